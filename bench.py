@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: batched acrobot Newton/Armijo swing-up on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_PER_GPU]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_PER_GPU] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,11 +17,17 @@ Workload (N=1): BASELINE cfg 3 -- 262,144 lanes per GPU, x0 = [th1, th2, 0, 0], 
 owns 262,144 lanes; ranks exchange one 64-byte all-reduce per host sync of the statistics.
 
 value = lane-iterations executed by all ranks / max-over-ranks wall time  ("Newton iterations/s";
-states/s = value * T).  Prints ONE JSON line on rank 0.  Secondary legs timed in the same process and
+states/s = value * T).  Prints ONE JSON line on rank 0.
+
+A plain run does what that figure needs and no more: it sets up, warms up, times the K steps (with the per-kernel
+HIP events of those same steps), writes the last step's results if --dump-outputs DIR is given (dump_newton_outputs),
+and prints the line.  --full adds everything else the line can hold: the box-state record, lane 0's parity against the
+golden trajectory, the CPU baselines and the secondary legs timed in the same process and
 reported inside that line (--extra-legs): "strong_scaling_cfg4" (BASELINE cfg 4: 1,048,576 lanes
 strong-scaled over the N ranks) and, at N = 1, "general_path" (the same workload on the general kernels that
 stream the tau1 planes), "cfg2" (BASELINE cfg 2: 4,096 lanes) and "mpc_cfg5" (BASELINE cfg 5).  --workload cfg4
-makes cfg 4 the main line; --workload mpc makes cfg 5 the main line (with its CPU baseline).
+makes cfg 4 the main line; --workload mpc makes cfg 5 the main line (--full: with its per-kernel times, its parity
+against the NumPy oracle and its CPU baseline).
 """
 from __future__ import annotations
 
@@ -113,18 +119,56 @@ def numpy_baseline(x0, x_ref, u_ref, lanes: int, iters: int):
                       f"one Python thread)", "seconds": dt, "lane_iterations": its}
 
 
+DUMP_SAMPLE_LANES = 512        # lanes whose whole trajectories --dump-outputs keeps (a fixed, seeded choice)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_sample(B: int) -> np.ndarray:
+    """The lanes whose per-stage arrays --dump-outputs writes: every lane of a batch of at most DUMP_SAMPLE_LANES,
+    otherwise lane 0 (the golden lane) and a sorted draw without replacement from default_rng(DUMP_SAMPLE_SEED) --
+    the same lanes in every run of the same batch size."""
+    if B <= DUMP_SAMPLE_LANES:
+        return np.arange(B)
+    pick = np.random.default_rng(DUMP_SAMPLE_SEED).choice(np.arange(1, B), DUMP_SAMPLE_LANES - 1, replace=False)
+    return np.concatenate([[0], np.sort(pick)])
+
+
+def write_dump(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy, float64 (integer results included: exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
+def dump_newton_outputs(out_dir: str, res) -> None:
+    """--dump-outputs: what the last timed solve returned to its caller (solver.SolveResult, this rank's shard).
+    The per-lane results of every lane (cost, gamma, n_iter, status, n_rollouts: 40 B per lane) and, of the lanes
+    dump_sample picks, the trajectories and gains (x, u, K, sigma: 64,032 B per lane at T = 500, 33 MB for 512 lanes);
+    sample_lanes holds their indices."""
+    import torch
+    lanes = dump_sample(res.cost.shape[0])
+    idx = torch.as_tensor(lanes, device=res.x.device)
+    arrays = {k: getattr(res, k).cpu().numpy() for k in ("cost", "gamma", "n_iter", "status", "n_rollouts")}
+    arrays.update({k: getattr(res, k)[idx].cpu().numpy() for k in ("x", "u", "K", "sigma")})
+    arrays["sample_lanes"] = lanes
+    write_dump(out_dir, arrays)
+
+
 def run_mpc(a):
     """--workload mpc: the cfg 5 line (mpc_line) printed as the bench's JSON line."""
-    print(json.dumps(mpc_line(a, a.batch, a.steps, a.warmup, a.cpu_lanes)), flush=True)
+    print(json.dumps(mpc_line(a, a.batch, a.steps, a.warmup, a.cpu_lanes, full=a.full, dump=a.dump_outputs)),
+          flush=True)
 
 
-def mpc_line(a, B, steps, warmup, cpu_lanes):
+def mpc_line(a, B, steps, warmup, cpu_lanes, full=True, dump=None):
     """BASELINE cfg 5: batched receding-horizon MPC (trajectory_tracking.py:8-69 / main.py task_4).
 
     One step = the whole tracking run of B disturbed initial states: the exact per-control-step QP
     solutions of all 500 windows (gym_mpc_gains; horizon a.horizon) plus the batched closed-loop RK4
     simulation under them (gym_track_rollout) and the lane-major results.  value = lanes x 500 control
-    steps / seconds per step.  cpu_lanes = 0: no CPU baseline (the parity sample is then 256 lanes)."""
+    steps / seconds per step.  ``full``: also the per-kernel times (one more run of the two kernels), the roofline
+    and the parity against the NumPy oracle; cpu_lanes = 0: no CPU baseline (the parity sample is then 256 lanes).
+    ``dump``: the directory the last timed step's results go to (x and u of the dump_sample lanes, K0)."""
     import torch
     from gymnast_optimalcontrol_amd import trajectory_tracking as tt
     from gymnast_optimalcontrol_amd.engine import AcrobotEngine  # noqa: F401
@@ -144,6 +188,19 @@ def mpc_line(a, B, steps, warmup, cpu_lanes):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     ctrl_steps = B * (N - 1)
+    if dump:
+        lanes = dump_sample(B)
+        idx = torch.as_tensor(lanes, device=x.device)
+        write_dump(dump, {"x": x[idx].cpu().numpy(), "u": u[idx].cpu().numpy(), "K0": K0.cpu().numpy(),
+                          "sample_lanes": lanes})
+    out = {"metric": "receding-horizon MPC control steps/s (BASELINE cfg 5)", "value": ctrl_steps / dt,
+           "unit": "control steps/s", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * dt,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": f"cfg5: {B} disturbed initial states (x_ref[0] + U(-0.1,0.1)^4) x 500 control "
+                                  f"steps, horizon {a.horizon}, exact QP solution per step, RK4 plant",
+                      "lanes": B, "horizon": a.horizon, "control_steps": N - 1}}
+    if not full:
+        return out
     # per-kernel times (HIP events on the engine's stream = torch's current stream).  The stream is kept busy
     # (torch.cuda._sleep) while the host enqueues the events and the two launches, so each interval is the kernel's
     # execution, not the host's Python time between two records on an idle GPU (round 3's line included it:
@@ -158,19 +215,14 @@ def mpc_line(a, B, steps, warmup, cpu_lanes):
     torch.cuda.synchronize()
     t_gain, t_roll = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
     roll_bytes = B * (N * 32 + (N - 1) * 16 + 32)                 # x (pairs) + u (planes) written, x0 read
-    out = {"metric": "receding-horizon MPC control steps/s (BASELINE cfg 5)", "value": ctrl_steps / dt,
-           "unit": "control steps/s", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * dt,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": f"cfg5: {B} disturbed initial states (x_ref[0] + U(-0.1,0.1)^4) x 500 control "
-                                  f"steps, horizon {a.horizon}, exact QP solution per step, RK4 plant",
-                      "lanes": B, "horizon": a.horizon, "control_steps": N - 1},
-           "kernels": {"mpc_gains_ms": t_gain, "track_rollout_ms": t_roll},
-           "roofline": {"bound": "hbm", "kernel": "track_rollout", "achieved": roll_bytes / (t_roll * 1e-3) / 1e9,
-                        "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": roll_bytes / (t_roll * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
-                        "kernel_name": "k_track_rollout_pair", "algorithmic_bytes_per_launch": roll_bytes,
-                        "note": "latency-bound: B/32 wavefronts (a lane pair per trajectory) each run 500 dependent "
-                                "RK4 steps; the bytes are the trajectories written and x0 read"}}
+    out.update({
+        "kernels": {"mpc_gains_ms": t_gain, "track_rollout_ms": t_roll},
+        "roofline": {"bound": "hbm", "kernel": "track_rollout", "achieved": roll_bytes / (t_roll * 1e-3) / 1e9,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": roll_bytes / (t_roll * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
+                     "kernel_name": "k_track_rollout_pair", "algorithmic_bytes_per_launch": roll_bytes,
+                     "note": "latency-bound: B/32 wavefronts (a lane pair per trajectory) each run 500 dependent "
+                             "RK4 steps; the bytes are the trajectories written and x0 read"}})
     traffic, ratio, _, src = pmc_traffic("track_rollout")
     if traffic is not None and B == 8192:
         out["roofline"].update({"traffic": traffic, "traffic_over_algorithmic": ratio, "traffic_source": src})
@@ -583,6 +635,14 @@ def main():
     ap.add_argument("--global-batch", type=int, default=None,
                     help="strong scaling: this many lanes in total, sharded over the ranks (cfg4: 1048576)")
     ap.add_argument("--max-iters", type=int, default=5000)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the box-state record, lane "
+                         "0's parity against the golden trajectory, the secondary legs (--extra-legs) and the CPU "
+                         "baselines; without it --extra-legs, --cpu-lanes and --numpy-lanes have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64; the "
+                         "per-lane results of every lane, the trajectories and gains of a fixed seeded sample of "
+                         "lanes; rank 0's shard)")
     ap.add_argument("--cpu-lanes", type=int, default=4096,
                     help="lanes of the bounded C-oracle CPU-baseline sample (about 10 s on 16 host cores)")
     ap.add_argument("--numpy-lanes", type=int, default=256,
@@ -677,15 +737,17 @@ def main():
     total = a.global_batch if strong else a.batch * world
     eng = AcrobotEngine()
     cold_s = process_warmup(eng, x_ref, u_ref)
-    box = None if a.no_box or rank != 0 else BoxMonitor(gd.local_device_index(local_rank))
+    box = None if not a.full or a.no_box or rank != 0 else BoxMonitor(gd.local_device_index(local_rank))
     main_leg = NewtonLeg(a, gd, eng, x_ref, u_ref, total, not a.no_timing,
                          u0_zero=False if a.u0_zero == "off" else None).run(a.steps, a.warmup, box)
     res = main_leg.res
     value = main_leg.value
+    if a.dump_outputs and rank == 0:
+        dump_newton_outputs(a.dump_outputs, res)
 
     # parity of the golden lane (rank 0 owns lane 0)
     parity = None
-    if rank == 0:
+    if rank == 0 and a.full:
         g = np.load(os.path.join(ROOT, "tests", "golden", "task2_reference_output.npz"))
         x0l, u0l = res.x[0].cpu().numpy(), res.u[0].cpu().numpy()
         st = res.status.cpu().numpy()
@@ -789,7 +851,7 @@ def main():
     main_leg.free()
 
     # secondary legs (same process, same JSON line)
-    legs = [s for s in a.extra_legs.split(",") if s] if a.workload == "newton" else []
+    legs = [s for s in a.extra_legs.split(",") if s] if a.workload == "newton" and a.full else []
     box_legs = {"main": main_leg.box}
     if "cfg4" in legs and not strong:
         leg = NewtonLeg(a, gd, eng, x_ref, u_ref, CFG4_LANES, not a.no_timing).run(a.extra_steps, 1, box)
@@ -889,7 +951,7 @@ def main():
             "of the region the SMU spent limited by the package power cap / a thermal limit (amd-smi throttle "
             "counters), energy_j and uj_per_lane_iteration from its energy counter.  A leg at power = cap with "
             "ppt_share near 1 runs at the SCLK the cap allows (DESIGN 6)")}
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         x0_all = make_x0(total, spread=a.spread)
         out["cpu_baseline"] = cpu_baseline(x0_all, x_ref, u_ref, a.cpu_lanes, a.max_iters)
         out["cpu_baseline"]["numpy"] = numpy_baseline(x0_all, x_ref, u_ref, a.numpy_lanes, a.numpy_iters)

@@ -442,7 +442,7 @@ def test_bench_spawns_ranks_on_the_gpu():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["GYM_DIST_BACKEND"] = "gloo"
-    args = ["--batch", "512", "--steps", "1", "--warmup", "0", "--no-cpu", "--extra-legs", ""]
+    args = ["--batch", "512", "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--extra-legs", ""]
 
     def line(n):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *args], env=env,

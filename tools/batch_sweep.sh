@@ -1,14 +1,15 @@
 #!/bin/bash
-# Throughput vs lanes per GPU (occupancy sweep) -- measurement tool.
+# Throughput vs lanes per GPU (occupancy sweep) -- measurement tool.  Logs go to $BENCH_LOGS (default bench_logs/).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
-mkdir -p gpurun_out
+LOGS=${BENCH_LOGS:-bench_logs}
+mkdir -p "$LOGS"
 for b in "$@"; do
-  timeout -k 10 300 python3 bench.py --steps 1 --warmup 1 --no-cpu --batch $b > gpurun_out/sweep_$b.log 2>&1
+  timeout -k 10 300 python3 bench.py --full --steps 1 --warmup 1 --no-cpu --batch $b > "$LOGS/sweep_$b.log" 2>&1
   rc=$?
-  python3 - "$b" <<'PY'
+  python3 - "$b" "$LOGS/sweep_$b.log" <<'PY'
 import json, re, sys
 b = sys.argv[1]
-s = open(f"gpurun_out/sweep_{b}.log").read()
+s = open(sys.argv[2]).read()
 m = re.search(r'(\{"metric.*\})', s)
 if m:
     d = json.loads(m.group(1))

@@ -30,9 +30,9 @@ for s in "$@"; do
     cfg3)    run fatal bench_cfg3 400 python -u bench.py --steps 3 --warmup 1 --no-cpu --extra-legs "" ;;
     cfg2)    run fatal bench_cfg2 300 python -u bench.py --batch 4096 --steps 5 --warmup 1 --no-cpu --extra-legs "" ;;
     stress)  run fatal bench_stress 400 python -u bench.py --workload stress --steps 2 --warmup 1 --no-cpu --extra-legs "" ;;
-    mpc)     run fatal bench_mpc 300 python -u bench.py --workload mpc --steps 20 --warmup 3 ;;
-    two)     run fatal bench_2rank 400 env GYM_DIST_BACKEND=gloo python -u bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu --extra-legs cfg4 ;;
-    full)    run fatal bench_full 900 python -u bench.py ;;
+    mpc)     run fatal bench_mpc 300 python -u bench.py --workload mpc --steps 20 --warmup 3 --full ;;
+    two)     run fatal bench_2rank 400 env GYM_DIST_BACKEND=gloo python -u bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu --extra-legs cfg4 ;;
+    full)    run fatal bench_full 900 python -u bench.py --full ;;
     trace3)  run fatal trace_cfg3 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace_cfg3" -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu --extra-legs "" ;;
     trace2)  run fatal trace_cfg2 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_cfg2" -o run --output-format csv -- python3 bench.py --batch 4096 --steps 5 --warmup 1 --no-cpu --extra-legs "" ;;
     fetch)   run fatal pmc_fetch 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_nt_" -d "$OUT/pmc_fetch" -o run --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu --no-timing --max-iters 20 --extra-legs "" ;;

@@ -31,7 +31,7 @@ for s in "$@"; do
     writem) run pmc_write_mpc 300 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_track|k_mpc" -d $OUT/pmc_write_mpc -o run --output-format csv -- python3 bench.py --workload mpc --steps 2 --warmup 1 ;;
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -v -p no:cacheprovider --tb=short --timeout 300 --timeout-method thread ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench_default 900 python -u bench.py ;;
+    bench) run bench_default 900 python -u bench.py --full ;;
     *) echo "unknown $s" ;;
   esac
 done

@@ -24,7 +24,7 @@ for s in "$@"; do
     tests_cand) step pytest_cand 600 $PYT tests/test_gpu_tail.py -m gpu -k "candidate_scratch" || exit $? ;;
     tests) step pytest_gpu 1100 $PYT tests -m gpu || exit $? ;;
     smoke) step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) step bench 600 python -u bench.py || exit $? ;;
+    bench) step bench 600 python -u bench.py --full || exit $? ;;
     bench_cfg2) step bench_cfg2 300 python -u bench.py --batch 4096 --steps 5 --warmup 1 --no-cpu --no-box --extra-legs "" || exit $? ;;
     bench_stress) step bench_stress 300 python -u bench.py --workload stress --steps 2 --warmup 1 --no-cpu --no-box --extra-legs "" || exit $? ;;
     trace2) step trace_cfg2 300 rocprofv3 --kernel-trace --stats -d $OUT/trace_cfg2 -o run --output-format csv -- python3 -u bench.py --batch 4096 --steps 5 --warmup 1 --no-cpu --no-box --extra-legs "" || exit $? ;;

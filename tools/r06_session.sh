@@ -63,16 +63,16 @@ for s in "$@"; do
     benchmain) step benchmain 400 python -u bench.py --steps 3 --warmup 1 --no-cpu --extra-legs "" || exit $? ;;
     tests) step pytest_gpu 1100 $PYT tests -m gpu || exit $? ;;
     smoke) step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) step bench 600 python -u bench.py || exit $? ;;
-    bench20) step bench20 600 python -u bench.py --steps 20 --warmup 2 --extra-legs "" || exit $? ;;
+    bench) step bench 600 python -u bench.py --full || exit $? ;;
+    bench20) step bench20 600 python -u bench.py --full --steps 20 --warmup 2 --extra-legs "" || exit $? ;;
     main20a) step main20a 400 python3 -u bench.py --steps 20 --warmup 5 --no-cpu --extra-legs "" || exit $? ;;
     main20b) step main20b 400 python3 -u bench.py --steps 20 --warmup 5 --no-cpu --extra-legs "" || exit $? ;;
-    driver) step bench_driver 900 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 || exit $? ;;
+    driver) step bench_driver 900 python3 -u bench.py --gpus 1 --full --steps 20 --warmup 5 || exit $? ;;
     trace3) step trace_cfg3 400 rocprofv3 --kernel-trace --stats -d $OUT/trace_cfg3 -o run --output-format csv -- python3 -u bench.py --steps 3 --warmup 1 --no-cpu --no-box --extra-legs "" || exit $? ;;
     two) GYM_DIST_BACKEND=gloo step bench_2rank 700 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-           --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 20 --warmup 5 || exit $? ;;
+           --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --full --steps 20 --warmup 5 || exit $? ;;
     four) GYM_DIST_BACKEND=gloo step bench_4rank 700 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-           --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 4 --steps 3 --warmup 1 || exit $? ;;
+           --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 4 --full --steps 3 --warmup 1 || exit $? ;;
     pd2cmp) GYM_ALLOW_FOREIGN_BUILD=1 step pd2_compare 300 python3 -u tools/compare_libs.py $LIB build_ab/libpd2.so --batch 131072 --iters 6 \
               --schedule pipelined || exit $? ;;
     pd2ab) for b in ${PD2_BATCHES:-131072 98304 196608 262144}; do
@@ -82,7 +82,7 @@ for s in "$@"; do
              GYM_ALLOW_FOREIGN_BUILD=1 step spread_ab_$b 400 python3 -u tools/ab_bench.py --batch $b --rounds 3 \
                build_ab/libA.so:pipe build_ab/libB.so:pipe build_ab/libC.so:pipe build_ab/libD.so:pipe || exit $?; done ;;
     lotest) step pytest_lo 600 $PYT tests/test_gpu_workloads.py -m gpu -k "two_wavefront or rank_share" || exit $? ;;
-    sharebench) step bench_share 600 python3 -u bench.py --steps 5 --warmup 2 --no-cpu --extra-legs cfg4share,cfg4 \
+    sharebench) step bench_share 600 python3 -u bench.py --full --steps 5 --warmup 2 --no-cpu --extra-legs cfg4share,cfg4 \
                   || exit $? ;;
     w3ab) for b in ${W3_BATCHES:-147456 163840 180224 196608}; do
              GYM_ALLOW_FOREIGN_BUILD=1 step w3_ab_$b 400 python3 -u tools/ab_bench.py --batch $b --rounds 3 $LIB:pipe \

@@ -1,15 +1,17 @@
 #!/bin/bash
 # Throughput of the solver schedules at the given batch sizes (measurement tool); SCHEDS selects them.
+# Logs go to $BENCH_LOGS (default bench_logs/).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
-mkdir -p gpurun_out
+LOGS=${BENCH_LOGS:-bench_logs}
+mkdir -p "$LOGS"
 for b in "$@"; do
   for s in ${SCHEDS:-serial pipelined persistent}; do
-    timeout -k 10 300 python3 bench.py --steps 2 --warmup 1 --no-cpu --extra-legs '' --batch $b --schedule $s > gpurun_out/sched_${b}_$s.log 2>&1
+    timeout -k 10 300 python3 bench.py --full --steps 2 --warmup 1 --no-cpu --extra-legs '' --batch $b --schedule $s > "$LOGS/sched_${b}_$s.log" 2>&1
     rc=$?
-    python3 - "$b" "$s" <<'PY'
+    python3 - "$b" "$s" "$LOGS/sched_${b}_$s.log" <<'PY'
 import json, re, sys
 b, s = sys.argv[1], sys.argv[2]
-t = open(f"gpurun_out/sched_{b}_{s}.log").read()
+t = open(sys.argv[3]).read()
 m = re.search(r'(\{"metric.*\})', t)
 if m:
     d = json.loads(m.group(1))
