@@ -22,7 +22,7 @@ EXPORTS = (
     "gym_pack_lanes", "gym_unpack_lanes", "gym_unpack_gains",
     "gym_rollout_open_loop", "gym_closed_loop", "gym_total_cost", "gym_backward_sweep", "gym_linearize",
     "gym_riccati_general",
-    "gym_newton_init", "gym_newton_iteration", "gym_newton_pipeline_split", "gym_newton_phase", "gym_newton_phase_kind",
+    "gym_newton_init", "gym_newton_init_warm", "gym_newton_iteration", "gym_newton_pipeline_split", "gym_newton_phase", "gym_newton_phase_kind",
     "gym_newton_run",
     "gym_newton_tail", "gym_newton_tail_scratch", "gym_newton_cand_scratch", "gym_newton_tail_lds",
     "gym_newton_finalize", "gym_newton_fill_states", "gym_placement_probe", "gym_newton_sigma",
@@ -33,7 +33,7 @@ EXPORTS = (
 KERNEL_KINDS = ("backward", "trial", "candidates", "retry", "stats", "phase_odd", "phase_even", "sigma", "run",
                 "tail")
 
-ABI_VERSION = 17        # GYM_ABI_VERSION of the header this binding mirrors
+ABI_VERSION = 18        # GYM_ABI_VERSION of the header this binding mirrors
 MAX_BP = 1 << 26         # GYM_MAX_BP
 FLAG_U0_ZERO = 1         # GYM_FLAG_U0_ZERO
 FLAG_X_CKPT = 2          # GYM_FLAG_X_CKPT
@@ -99,6 +99,7 @@ _SIGS = {
     "gym_linearize": [_MP, _WP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P],
     "gym_riccati_general": [_P] * 12 + [_I64, _I64, _I32, _P],
     "gym_newton_init": [_MP, _WP, _P, _BP, _P],
+    "gym_newton_init_warm": [_MP, _WP, _P, _P, _P, _BP, _P],
     "gym_newton_iteration": [_MP, _WP, _AP, _BP, _I32, _P],
     "gym_newton_pipeline_split": [_BP, C.POINTER(C.c_int64)],
     "gym_newton_phase_kind": [_BP, C.POINTER(C.c_int32)],

@@ -1262,9 +1262,104 @@ __global__ __launch_bounds__(TILE_THREADS) void k_unpack_tiled(Src src, double* 
     }
 }
 
+// Lane-major controls (B, T, 2), rows selected through a lane map, -> planes (T, 2, Bp): the warm start's input
+// side (gym_newton_init_warm).  The mirror image of k_unpack_tiled: one workgroup moves the tile of one 64-lane
+// group x GP_TS knots.  Each lane's GP_TS (tau1, tau2) pairs -- contiguous in the lane-major array -- are read by
+// consecutive threads with 16-byte loads (512 B runs per lane), staged in LDS as [plane][knot][lane] with the
+// 65-double row pitch (consecutive knots of one lane land 65 doubles apart: conflict-free), and every plane row is
+// written as one coalesced 512 B row of 64 lanes.  Internal lane l takes row map[l] (NULL: l); padding lanes
+// (l >= B) read nothing and are zero-filled.  grid (Bp / 64) x ceil(T / GP_TS).
+constexpr int GP_TS = 32;
+__global__ __launch_bounds__(TILE_THREADS) void k_gather_pack_u(const double2* __restrict__ src,
+                                                                double* __restrict__ dst,
+                                                                const int64_t* __restrict__ map, int64_t B,
+                                                                int64_t Bp, int T) {
+    __shared__ double tile[2 * GP_TS * TILE_PITCH];
+    __shared__ int64_t rows_of[BLK];                        // input row of each lane of the group
+    const int64_t g0 = (int64_t)blockIdx.x * BLK;          // first lane of the group
+    const int t0 = (int)blockIdx.y * GP_TS;
+    const int ts = (T - t0 < GP_TS) ? T - t0 : GP_TS;
+    if (threadIdx.x < BLK) {
+        const int64_t l = g0 + threadIdx.x;
+        rows_of[threadIdx.x] = (l < B) ? (map ? map[l] : l) : -1;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < ts * BLK; i += TILE_THREADS) {
+        const int ln = i / ts, k = i - ln * ts;
+        const int64_t row = rows_of[ln];
+        const double2 v = row >= 0 ? ld_nt(src + row * T + t0 + k) : make_double2(0.0, 0.0);
+        tile[k * TILE_PITCH + ln] = v.x;
+        tile[(GP_TS + k) * TILE_PITCH + ln] = v.y;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * ts * BLK; i += TILE_THREADS) {
+        const int ln = i & (BLK - 1), r = i >> 6;          // r = plane * ts + knot
+        const int p = r >= ts, k = r - p * ts;
+        st_nt(dst + pix(t0 + k, p, 2, g0 + ln, Bp), tile[(p * GP_TS + k) * TILE_PITCH + ln]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // kernels: batched Newton / Armijo solver (newton_Algorithm :298-398)
 // ------------------------------------------------------------------------------------------
+// Open-loop rollout of the control planes u with its cost, as an Armijo trial forms them (rollout_cform): per stage
+// the cost of (x_t, u_t) through stage_cost<U0Z>, then x_{t+1} = rk4_fast(x_t, tau2_t), the terminal cost last.  The
+// trial's controls are the values it stored, so the rollout of a control sequence a trial produced returns that
+// trial's states and cost bit for bit (gym_newton_init_warm).  Every knot of xn is stored (valid with
+// GYM_FLAG_X_CKPT, as k_init's).
+template <bool U0Z>
+__device__ __forceinline__ double rollout_warm(const Dyn& m, const KW& w, const double* __restrict__ u,
+                                               const double* __restrict__ xr, const double* __restrict__ ur,
+                                               double2* __restrict__ xn, int64_t l, int64_t Bp, int N, double n0,
+                                               double n1, double n2, double n3) {
+    const int T = N - 1;
+    const gym::PolyRegs pk = gym::poly_vgprs();
+    double J = 0.0;
+    xn[wix(0, 0, 2, l, Bp)] = make_double2(n0, n1);
+    xn[wix(0, 1, 2, l, Bp)] = make_double2(n2, n3);
+    for (int t = 0; t < T; ++t) {
+        const double* urt = ur + 2 * t;
+        const double v1 = u[pix(t, 1, 2, l, Bp)];
+        const double f0 = U0Z ? 0.0 : u[pix(t, 0, 2, l, Bp)] - urt[0], f1 = v1 - urt[1];
+        J = stage_cost<U0Z>(J, w.Q, w.R, n0, n1, n2, n3, xr + 4 * t, f0, f1);
+        gym::rk4_fast(m, n0, n1, n2, n3, v1, pk);
+        xn[wix(t + 1, 0, 2, l, Bp)] = make_double2(n0, n1);
+        xn[wix(t + 1, 1, 2, l, Bp)] = make_double2(n2, n3);
+    }
+    return J + xcost(w.QT, n0, n1, n2, n3, xr + 4 * T);
+}
+
+// Warm start (gym_newton_init_warm): k_init's reset, with x[0] rolled out from x0 under the caller's controls
+// (already packed into u[0]) and each lane's status taken from status_init.  Internal lane l takes row map[l] of x0
+// and status_init (NULL: l); per-lane references are indexed by the internal lane, as everywhere.
+template <bool U0Z, bool RL>
+__global__ __launch_bounds__(BLK) void k_init_warm(Dyn m, KW w, const double* __restrict__ x0,
+                                                   const int32_t* __restrict__ status_init,
+                                                   const int64_t* __restrict__ map, const double* __restrict__ u,
+                                                   const double* __restrict__ xr, const double* __restrict__ ur,
+                                                   double2* __restrict__ xn, double* __restrict__ cost,
+                                                   int32_t* __restrict__ status, int32_t* __restrict__ n_iter,
+                                                   int32_t* __restrict__ res_buf, int32_t* __restrict__ n_roll,
+                                                   double* __restrict__ gamma, double* __restrict__ smax,
+                                                   double* __restrict__ dJ, int64_t B, int64_t Bp, int N) {
+    const int64_t l = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (l >= Bp) return;
+    n_iter[l] = 0; res_buf[l] = 0; n_roll[l] = 0; gamma[l] = 0.0; smax[l] = 0.0; dJ[l] = 0.0;
+    if (l >= B) {
+        status[l] = GYM_PAD;
+        cost[l] = 0.0;
+        return;
+    }
+    const int64_t row = map ? map[l] : l;
+    // a finished lane keeps its status and never iterates (its result: buffer 0); anything else is an interrupted
+    // lane (GYM_ACTIVE, GYM_MAX_ITERS) or out of contract, and iterates
+    const int32_t s_in = status_init ? status_init[row] : (int32_t)GYM_ACTIVE;
+    status[l] = (s_in == GYM_CONVERGED || s_in == GYM_LS_FAILED) ? s_in : (int32_t)GYM_ACTIVE;
+    cost[l] = rollout_warm<U0Z>(m, w, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
+                                lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), xn, l, Bp, N, x0[4 * row + 0],
+                                x0[4 * row + 1], x0[4 * row + 2], x0[4 * row + 3]);
+}
+
 template <bool RL = false>
 __global__ __launch_bounds__(BLK) void k_init(Dyn m, KW w, const double* __restrict__ x0,
                                               const double* __restrict__ u, const double* __restrict__ xr,
@@ -3312,6 +3407,32 @@ int gym_newton_init(const gym_model* m, const gym_weights* w, const double* x0, 
                        dim3(BLK), 0, st, Dyn(*m), kw(*w), x0, b->u[0], b->x_ref, b->u_ref,
                        (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax,
                        b->dJ, b->B, b->Bp, b->N);
+    return launch_status();
+}
+
+int gym_newton_init_warm(const gym_model* m, const gym_weights* w, const double* x0, const double* u_init,
+                         const int32_t* status_init, const gym_batch* b, void* s) {
+    if (!m || !w || !x0 || !u_init || bad_batch(b) || ((uintptr_t)u_init & 15)) return GYM_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    const int T = b->N - 1;
+    if ((T + GP_TS - 1) / GP_TS > 65535) return GYM_EINVAL;   // the gather-pack's grid.y
+    hipError_t e = hipSuccess;
+    if (b->flags & GYM_FLAG_U0_ZERO) {  // as gym_newton_init: the trials never write the u0 planes
+        e = hipMemsetAsync(b->u[1], 0, sizeof(double) * 2 * (size_t)T * b->Bp, st);
+        if (e != hipSuccess) return (int)e;
+    }
+    e = hipMemsetAsync(b->counters, 0, sizeof(int32_t) * 4, st);
+    if (e != hipSuccess) return (int)e;
+    e = hipMemsetAsync(b->stats, 0, sizeof(double) * 24, st);
+    if (e != hipSuccess) return (int)e;
+    // u[0] <- the caller's controls (every element of the planes is written: padding lanes zero)
+    hipLaunchKernelGGL(k_gather_pack_u, dim3((unsigned)(b->Bp / BLK), (unsigned)((T + GP_TS - 1) / GP_TS)),
+                       dim3(TILE_THREADS), 0, st, (const double2*)u_init, b->u[0], b->lane_map, b->B, b->Bp, T);
+    int rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(CAND_SEL(b, k_init_warm), dim3(grid_for(b->Bp, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w), x0,
+                       status_init, b->lane_map, b->u[0], b->x_ref, b->u_ref, (double2*)b->x[0], b->cost, b->status,
+                       b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax, b->dJ, b->B, b->Bp, b->N);
     return launch_status();
 }
 

@@ -38,7 +38,7 @@ import torch
 
 from . import _lib
 from .engine import AcrobotEngine, padded, F64
-from .params import MAX_LINE_SEARCH_ITERS
+from .params import DT, MAX_LINE_SEARCH_ITERS
 
 STAT_FIELDS = ("n_active", "sum_cost", "sum_smax2", "lanes_ran", "n_retry", "n_converged", "n_failed", "n_rollouts")
 
@@ -69,6 +69,70 @@ class SolveResult:
     lowocc_lane_iterations: int = 0         # lane-iterations run in the low-occupancy regime (maybe_compact)
     tail_from_iteration: int | None = None  # the outer iteration the straggler tail took over at (None: no tail)
     tail_iterations: int = 0                # outer iterations the tail ran (its slowest lane's, up to the last one)
+
+    def save_npz(self, path, t=None, dt: float = DT):
+        """Write the per-lane results as one .npz in the reference's wire format (main.py:74-79, np.savez(x=, u=,
+        t=)): x (B,N,4), u (B,T,2), t (N,) = arange(N) * dt unless given, plus cost, status, n_iter, gamma,
+        n_rollouts, K and sigma, which load_checkpoint / BatchedNewtonSolver.resume continue from.  Host I/O only:
+        tensors on any device."""
+        a = {k: getattr(self, k).detach().cpu().numpy() for k in CHECKPOINT_KEYS}
+        N = a["x"].shape[1]
+        a["t"] = np.arange(N) * float(dt) if t is None else np.asarray(t, dtype=np.float64)
+        if a["t"].shape != (N,):
+            raise ValueError(f"t must hold the {N} knot times, got {a['t'].shape}")
+        np.savez(path, **a)
+
+
+CHECKPOINT_KEYS = ("x", "u", "cost", "status", "n_iter", "gamma", "n_rollouts", "K", "sigma")
+
+
+@dataclass
+class Checkpoint:
+    """Per-lane iterates to continue from (load_checkpoint): SolveResult's per-lane fields and the knot times."""
+    x: torch.Tensor          # (B,N,4)
+    u: torch.Tensor          # (B,T,2)
+    t: torch.Tensor          # (N,)
+    cost: torch.Tensor       # (B,)   NaN where the file had none
+    status: torch.Tensor     # (B,)   int32
+    n_iter: torch.Tensor     # (B,)   int32
+    gamma: torch.Tensor      # (B,)
+    n_rollouts: torch.Tensor # (B,)   int32
+    K: torch.Tensor          # (B,T,2,4)
+    sigma: torch.Tensor      # (B,T,2)
+
+
+def load_checkpoint(path, device="cpu") -> Checkpoint:
+    """Read a checkpoint written by SolveResult.save_npz -- or a trajectory file of the reference itself
+    (acrobot_optimal_trajectory.npz: x (N,4), u (N-1 or N,2) without a lane axis, t, nothing else), which loads as a
+    one-lane checkpoint with the lane ACTIVE, n_iter = 0 and no gains.  Tensors go to ``device``."""
+    with np.load(path) as d:
+        a = {k: d[k] for k in d.files}
+    for k in ("x", "u"):
+        if k not in a:
+            raise ValueError(f"{path}: not a trajectory file (no '{k}')")
+    x, u = np.asarray(a["x"], dtype=np.float64), np.asarray(a["u"], dtype=np.float64)
+    if x.ndim == 2 and u.ndim == 2:
+        x, u = x[None], u[None]
+    if x.ndim != 3 or x.shape[2] != 4 or u.ndim != 3 or u.shape[2] != 2 or u.shape[0] != x.shape[0]:
+        raise ValueError(f"{path}: x {x.shape} / u {u.shape} are not (B,N,4) / (B,T,2) trajectories")
+    B, N = x.shape[:2]
+    if u.shape[1] == N:          # a control row per knot: the last one is unused (trajectory_generation.py:301-303)
+        u = u[:, :-1]
+    if u.shape[1] != N - 1:
+        raise ValueError(f"{path}: x has {N} knots but u has {u.shape[1]} controls (expected {N - 1})")
+    T = N - 1
+    full = {"x": x, "u": np.ascontiguousarray(u),
+            "t": np.asarray(a["t"], dtype=np.float64) if "t" in a else np.arange(N) * DT,
+            "cost": np.full(B, np.nan), "status": np.full(B, _lib.ACTIVE, np.int32), "n_iter": np.zeros(B, np.int32),
+            "gamma": np.zeros(B), "n_rollouts": np.zeros(B, np.int32), "K": np.zeros((B, T, 2, 4)),
+            "sigma": np.zeros((B, T, 2))}
+    for k in CHECKPOINT_KEYS[2:]:
+        if k in a:
+            v = np.asarray(a[k], dtype=full[k].dtype)
+            if v.shape != full[k].shape:
+                raise ValueError(f"{path}: '{k}' has shape {v.shape}, expected {full[k].shape}")
+            full[k] = v
+    return Checkpoint(**{k: torch.as_tensor(v).to(device) for k, v in full.items()})
 
 
 class PlacementPool:
@@ -250,6 +314,7 @@ class BatchedNewtonSolver:
         if u0_zero and not ref_u0_zero:
             raise ValueError("u0_zero=True requires u_ref[:, 0] == 0")
         self.u0_zero = ref_u0_zero if u0_zero is None else bool(u0_zero)
+        self._u0_cleared = False   # the flag is off for one warm-started solve whose u_init has tau1 != 0 (init)
         # state checkpointing (GYM_FLAG_X_CKPT, opt-in): trials store x at every CKPT_INTERVAL-th knot only
         # and the sweep re-integrates the rest -- bit-identical results, 48 B/stage less traffic, but +0.75 RK4
         # per sweep stage: on MI355X the solver is as VALU- as HBM-limited and this measured 13% slower
@@ -582,19 +647,79 @@ class BatchedNewtonSolver:
                 pass
 
     # --- the three stream-ordered phases (no host synchronisation inside) -----------------
-    def init(self, x0, _ref_perm=None):
+    def _warm_inputs(self, u_init, status_init):
+        """The warm start's inputs as the C-ABI takes them: u_init (B,T,2) fp64 and status_init (B) int32 or None,
+        contiguous on the engine device, u_init 16-byte aligned.  Wrong shapes or dtypes: ValueError."""
+        if isinstance(u_init, torch.Tensor) and u_init.dtype != F64:
+            raise ValueError(f"u_init must be float64, got {u_init.dtype}")
+        u = self.eng.t(u_init)
+        if tuple(u.shape) != (self.B, self.T, 2):
+            raise ValueError(f"u_init must be ({self.B},{self.T},2), got {tuple(u.shape)}")
+        if u.data_ptr() % 16:
+            u = u.clone()
+        st = None
+        if status_init is not None:
+            st = status_init if isinstance(status_init, torch.Tensor) else torch.as_tensor(np.asarray(status_init))
+            if st.dtype.is_floating_point or st.dtype.is_complex or st.dtype == torch.bool:
+                raise ValueError(f"status_init must hold integer status codes, got {st.dtype}")
+            if tuple(st.shape) != (self.B,):
+                raise ValueError(f"status_init must be ({self.B},), got {tuple(st.shape)}")
+            st = st.to(device=self.eng.device, dtype=torch.int32).contiguous()
+        return u, st
+
+    def _set_u0_zero(self, on: bool):
+        self.u0_zero = bool(on)
+        if on:
+            self.batch.flags |= _lib.FLAG_U0_ZERO
+        else:
+            self.batch.flags &= ~_lib.FLAG_U0_ZERO
+
+    def _restore_u0_zero(self):
+        if self._u0_cleared:
+            self._u0_cleared = False
+            self._set_u0_zero(True)
+
+    def init(self, x0, u_init=None, status_init=None, _ref_perm=None, _lane_map=None):
+        """Start a solve from x0 (B,4): the reference's u = 0 (gym_newton_init), or, with ``u_init`` (B,T,2), from the
+        caller's control iterate (gym_newton_init_warm: x rolled out from x0 under u_init with the Armijo trials'
+        arithmetic, so a trial's own controls give back its states and cost bit for bit).  ``status_init`` (B)
+        integer codes, with u_init only: lanes given CONVERGED or LS_FAILED keep that status and never iterate, any
+        other value is an interrupted lane and iterates.  Iteration counts restart at 0 either way.
+        A solver built with the tau1 planes skipped (u0_zero) whose u_init has a non-zero tau1 runs this solve on
+        the general path (bit-identical by construction) and takes the flag back at the end of solve() or at the
+        next init()."""
         self.lane_order = None
+        self._restore_u0_zero()   # a warm start with tau1 != 0 that was not followed by solve()'s end
         x0 = self.eng.t(x0).reshape(-1, 4)
         if x0.shape[0] != self.B:
             raise ValueError(f"x0 must hold {self.B} lanes, got {x0.shape[0]}")
+        if u_init is None and status_init is not None:
+            raise ValueError("status_init needs u_init (a lane's status belongs to its control iterate)")
+        if u_init is not None:
+            u_init, status_init = self._warm_inputs(u_init, status_init)
         if self.ref_lane:   # the references in the lanes' internal order (solve()'s Morton order, or the caller's)
             self.xr_buf[:self.B] = self._xr_in if _ref_perm is None else self._xr_in[_ref_perm]
             self.ur_buf[:self.B] = self._ur_in if _ref_perm is None else self._ur_in[_ref_perm]
         self._x0 = x0
         if self._pl is not None:
             self._placement_start()
-        _lib.check(self.eng.lib.gym_newton_init(C.byref(self.eng.model), C.byref(self.eng._w), x0.data_ptr(),
-                                                C.byref(self.batch), self.eng.stream), "gym_newton_init")
+        if u_init is None:
+            _lib.check(self.eng.lib.gym_newton_init(C.byref(self.eng.model), C.byref(self.eng._w), x0.data_ptr(),
+                                                    C.byref(self.batch), self.eng.stream), "gym_newton_init")
+        else:
+            if self.u0_zero and bool((u_init[..., 0] != 0).any().item()):
+                self._set_u0_zero(False)
+                self._u0_cleared = True
+            # the caller's arrays go over unpermuted: internal lane i takes row lane_map[i] (the inverse direction of
+            # finalize's use of the field)
+            self.batch.lane_map = None if _lane_map is None else _lane_map.data_ptr()
+            try:
+                _lib.check(self.eng.lib.gym_newton_init_warm(C.byref(self.eng.model), C.byref(self.eng._w),
+                                                             x0.data_ptr(), u_init.data_ptr(), _lib.ptr(status_init),
+                                                             C.byref(self.batch), self.eng.stream),
+                           "gym_newton_init_warm")
+            finally:
+                self.batch.lane_map = None
         self.k = 0
         self._capture_start(self.capture_lanes or [])
         self._serial_now = False   # the low-occupancy regime (maybe_compact / _enter_low_occupancy)
@@ -742,7 +867,10 @@ class BatchedNewtonSolver:
         return x, u, K, s
 
     def states(self, buf: int) -> torch.Tensor:
-        """Every knot of state buffer ``buf`` (SoA (N,2,Bp,2)), rebuilt from its checkpoints if checkpointing."""
+        """Every knot of state buffer ``buf`` (SoA (N,2,Bp,2)), rebuilt from its checkpoints if checkpointing.
+        This is the solver's live stream buffer, not a copy: the next iteration overwrites it, and once this solver
+        is gone the PlacementPool may hand the same memory to the next solver of the same shape.  Clone what must
+        outlive either (unpack() already copies)."""
         _lib.check(self.eng.lib.gym_newton_fill_states(C.byref(self.eng.model), C.byref(self.batch), int(buf),
                                                        self.eng.stream), "gym_newton_fill_states")
         return self.x[buf]
@@ -896,12 +1024,17 @@ class BatchedNewtonSolver:
 
     # --- full solve ----------------------------------------------------------------------
     def solve(self, x0, max_iters: int, reduce_stats=None, sync_every: int = 1, log_every: int = 0,
-              keep_stats: bool = False) -> SolveResult:
+              keep_stats: bool = False, u_init=None, status_init=None) -> SolveResult:
         """Run until every lane (of every rank, if ``reduce_stats`` all-reduces) is done or max_iters.
 
         With ``reorder`` (default) the lanes are solved in the Morton order of their initial states
         (``morton_order``) and the results are returned in the caller's order; the device buffers then hold
-        lane ``lane_order[i]`` of the input at position i."""
+        lane ``lane_order[i]`` of the input at position i.
+
+        ``u_init`` (B,T,2) / ``status_init`` (B): warm start from the caller's control iterate (see init()); the
+        arrays are handed over in the caller's order (the Morton permutation goes to the device as the init call's
+        lane map, no permuted copy is made).  n_iter, n_rollouts, the histories and the captures of the result
+        count from this call (resume() adds a checkpoint's)."""
         torch.cuda.synchronize(self.eng.device)
         t0 = time.perf_counter()
         self.max_iters = int(max_iters)
@@ -909,8 +1042,19 @@ class BatchedNewtonSolver:
         if self.reorder and self.B > 1:
             x0 = self.eng.t(x0).reshape(-1, 4)
             perm = morton_order(x0)
-            x0 = x0[perm]
-        self.init(x0, _ref_perm=perm)
+            if u_init is None:
+                x0 = x0[perm]
+        try:
+            return self._solve(x0, perm, t0, reduce_stats, sync_every, log_every, keep_stats, u_init, status_init)
+        finally:
+            self._restore_u0_zero()
+
+    def _solve(self, x0, perm, t0, reduce_stats, sync_every, log_every, keep_stats, u_init, status_init):
+        max_iters = self.max_iters
+        if u_init is None:
+            self.init(x0, status_init=status_init, _ref_perm=perm)
+        else:
+            self.init(x0, u_init=u_init, status_init=status_init, _ref_perm=perm, _lane_map=perm)
         self.lane_order = perm
         if perm is not None and self.capture_lanes is not None:
             inv = torch.empty_like(perm)
@@ -969,6 +1113,37 @@ class BatchedNewtonSolver:
         res["lowocc_lane_iterations"] = int(lowocc)
         return SolveResult(x=x, u=u, K=K, sigma=s, n_iter=n_iter, iterations=iters,
                            lane_iterations=int(n_iter.sum().item()), seconds=secs, stats_log=log, **res)
+
+
+    def resume(self, ckpt: Checkpoint, max_iters: int, **solve_kw) -> SolveResult:
+        """Continue a checkpoint (load_checkpoint) for up to ``max_iters`` further iterations:
+        solve(ckpt.x[:, 0], max_iters, u_init=ckpt.u, status_init=ckpt.status), merged with the checkpoint.
+
+        A lane's bits do not depend on the schedule, its position or the launch it runs in, and the warm rollout is
+        the Armijo trial's own, so a solve split at iteration k and resumed returns the uninterrupted solve's x, u,
+        cost, status, n_iter, gamma and n_rollouts bit for bit (and K, sigma of every lane that iterated again).
+        The merge: n_iter and n_rollouts are the checkpoint's plus this segment's; lanes the checkpoint had finished
+        (CONVERGED / LS_FAILED: they do not iterate) keep its cost, gamma, K and sigma, as the device ran no sweep
+        for them; so do K and sigma of lanes that ran no iteration here, and gamma of lanes that accepted no step
+        here.  ``iterations``, ``lane_iterations``, the histories, the statistics log and the captures count this
+        segment only."""
+        dev = self.eng.device
+        c = {k: getattr(ckpt, k).to(dev) for k in CHECKPOINT_KEYS}
+        if c["x"].ndim != 3 or c["x"].shape[0] != self.B or c["x"].shape[1] != self.N:
+            raise ValueError(f"the checkpoint holds x {tuple(c['x'].shape)}, this solver ({self.B},{self.N},4)")
+        r = self.solve(c["x"][:, 0].contiguous(), max_iters, u_init=c["u"], status_init=c["status"], **solve_kw)
+        done = (c["status"] == _lib.CONVERGED) | (c["status"] == _lib.LS_FAILED)
+        ran = (r.n_iter > 0) & ~done
+        stepped = ran & ((r.n_iter - (r.status == _lib.LS_FAILED).to(r.n_iter.dtype)) > 0)
+        r.cost = torch.where(done, c["cost"].to(r.cost.dtype), r.cost)
+        r.gamma = torch.where(stepped, r.gamma, c["gamma"].to(r.gamma.dtype))
+        keep = (~ran).nonzero().flatten()       # rows only: K is the largest result (8 GB at 262,144 lanes)
+        if keep.numel():
+            r.K[keep] = c["K"][keep].to(r.K.dtype)
+            r.sigma[keep] = c["sigma"][keep].to(r.sigma.dtype)
+        r.n_iter = r.n_iter + c["n_iter"].to(r.n_iter.dtype)
+        r.n_rollouts = r.n_rollouts + c["n_rollouts"].to(r.n_rollouts.dtype)
+        return r
 
 
 def morton_order(x0: torch.Tensor, bits: int = 10) -> torch.Tensor:
@@ -1129,11 +1304,12 @@ def tail_loop(solver, k: int, max_iters: int, reduce_stats, log_every: int, keep
 def newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, gamma_0=1.0,
                        max_ls=MAX_LINE_SEARCH_ITERS, engine: AcrobotEngine | None = None, hist_len=0,
                        reduce_stats=None, pipeline: bool | None = None,
-                       persistent: bool | None = None, capture_lanes=None) -> SolveResult:
-    """Batched newton_Algorithm: x0 (B,4) -> SolveResult (device tensors)."""
+                       persistent: bool | None = None, capture_lanes=None, u_init=None) -> SolveResult:
+    """Batched newton_Algorithm: x0 (B,4) -> SolveResult (device tensors).  ``u_init`` (B,T,2): start from these
+    controls instead of u = 0 (BatchedNewtonSolver.init)."""
     eng = engine or AcrobotEngine()
     x0 = eng.t(x0).reshape(-1, 4)
     solver = BatchedNewtonSolver(eng, x_ref, u_ref, x0.shape[0], tol=tol, beta=beta, c=c, gamma_0=gamma_0,
                                  max_ls=max_ls, hist_len=hist_len, pipeline=pipeline, persistent=persistent,
                                  capture_lanes=capture_lanes)
-    return solver.solve(x0, max_iters, reduce_stats=reduce_stats)
+    return solver.solve(x0, max_iters, reduce_stats=reduce_stats, u_init=u_init)

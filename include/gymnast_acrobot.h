@@ -43,14 +43,16 @@
 extern "C" {
 #endif
 
-#define GYM_ABI_VERSION 17
+#define GYM_ABI_VERSION 18
 #define GYM_MAX_BP (1LL << 26) /* lane stride limit: stream offsets are 32-bit inside one stage      */
 
 /* gym_batch.flags */
 #define GYM_FLAG_U0_ZERO 1  /* u_ref[:,0] == 0: the unactuated tau1 channel stays exactly zero (u0 starts
                              * at 0 and sigma0 = -(u0 - ur0) = -0, dynamics.py:205 ignores it), so the
                              * solver neither reads nor writes its planes; both u buffers are zeroed by
-                             * gym_newton_init. Results are bit-identical to the general path.          */
+                             * gym_newton_init (gym_newton_init_warm: u[1] zeroed, u[0] packed from a u_init
+                             * whose tau1 the caller guarantees to be exactly 0). Results are bit-identical
+                             * to the general path.                                                         */
 #define GYM_FLAG_X_CKPT 2   /* state checkpointing: the Armijo trials store x only at the checkpoint knots
                              * t % GYM_CKPT_INTERVAL == 0 and t == N-1; the backward sweep re-integrates the
                              * knots between two checkpoints (RK4 from the checkpoint with the stored controls,
@@ -151,7 +153,8 @@ typedef struct gym_batch {
     double* hist_cost;  /* optional (hist_len, Bp): J after iteration k            */
     double* hist_smax;  /* optional (hist_len, Bp): max|sigma| of iteration k      */
     const int64_t* lane_map; /* optional (B): lane i's results go to row lane_map[i] of the lane-major outputs
-                         * of gym_newton_finalize / gym_newton_sigma (a permutation; NULL: identity)  */
+                         * of gym_newton_finalize / gym_newton_sigma, and lane i takes row lane_map[i] of the
+                         * lane-major inputs of gym_newton_init_warm (a permutation; NULL: identity)  */
     gym_timing* timing; /* [host] optional kernel timing (NULL: none)               */
     /* optional (ABI 13) candidate scratch of the post-trial Armijo search.  Used by every post-trial launch when
      * cand_slots > 0 and neither GYM_FLAG_X_CKPT nor GYM_FLAG_RUN_SINGLE is set: gym_newton_iteration and
@@ -235,6 +238,20 @@ int gym_riccati_general(const double* A, const double* Bm, const double* Q, cons
 /* ---------------- batched Newton / Armijo solver (newton_Algorithm, :298-398) ---------------- */
 /* Open-loop init (u = 0, :311-312), J_0 (:319), status/counters reset.  x0 (B,4) lane-major. */
 int gym_newton_init(const gym_model* m, const gym_weights* w, const double* x0, const gym_batch* bt, void* stream);
+/* Warm start / resume (ABI 18): newton_Algorithm (:311-319) from a caller's control iterate instead of u = 0 (the
+ * reference saves one with np.savez(x=, u=, t=), main.py:74-79).  u_init (B,T,2) lane-major, 16-byte aligned, is
+ * packed into the planes u[0] (one tiled gather-pack launch, padding lanes zero), x[0] is its open-loop rollout from
+ * x0 (:311-312, simulate_open_loop :74-87) and cost = J_0 (:319), with the Armijo trials' own RK4 and stage-cost
+ * arithmetic in their order: a control sequence that a trial produced gives back that trial's states and cost bit for
+ * bit, so a solve split at any iteration and resumed equals the uninterrupted one.  Every knot of x[0] is stored
+ * (valid with GYM_FLAG_X_CKPT).  status_init (B) or NULL = all ACTIVE: a lane given GYM_CONVERGED or GYM_LS_FAILED
+ * keeps that status and never iterates (its x, u, cost stay in buffer 0, res_buf = 0); GYM_ACTIVE, GYM_MAX_ITERS and
+ * any other value mean ACTIVE.  bt->lane_map, if set, is used on the INPUT side: internal lane i takes row lane_map[i]
+ * of x0, u_init and status_init (per-lane references stay in internal lane order).  Counters as gym_newton_init:
+ * n_iter restarts at 0 and the next call is iteration k = 0 (buffers x/u[0] current).  With GYM_FLAG_U0_ZERO both
+ * tau planes are packed and u[1] zeroed; tau1 of u_init must then be exactly 0 (the caller's contract). */
+int gym_newton_init_warm(const gym_model* m, const gym_weights* w, const double* x0, const double* u_init,
+                         const int32_t* status_init, const gym_batch* bt, void* stream);
 /* One outer iteration k for every ACTIVE lane: backward sweep (K1, cs), Armijo trial 1 (gamma0) fused with its cost,
  * parallel candidate rollouts gamma0*beta^j (j = 1..max_ls-1) for lanes that rejected trial 1, accepted-
  * candidate rollout, lane status update, then device statistics into bt->stats:
