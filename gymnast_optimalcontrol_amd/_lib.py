@@ -28,6 +28,7 @@ EXPORTS = (
     "gym_newton_finalize", "gym_newton_fill_states", "gym_placement_probe", "gym_newton_sigma",
     "gym_gamma_sweep", "gym_newton_gamma_sweep",
     "gym_tv_lqr_gains", "gym_dare_fixed_point", "gym_mpc_gains", "gym_lq_forward", "gym_track_rollout", "gym_track_rollout_ex",
+    "gym_mpc_gains_all", "gym_mpc_box_workspace", "gym_mpc_box_qp", "gym_mpc_box_rollout",
     "gym_timing_create", "gym_timing_destroy", "gym_timing_collect",
 )
 KERNEL_KINDS = ("backward", "trial", "candidates", "retry", "stats", "phase_odd", "phase_even", "sigma", "run",
@@ -121,6 +122,11 @@ _SIGS = {
     "gym_lq_forward": [_P, _P, _I32, _P, _P, _I32, _D, _P, _P, _I32, _P, _P, _P],
     "gym_track_rollout": [_MP, _P, _P, _P, _P, _I64, _I32, _P, _P, _P],
     "gym_track_rollout_ex": [_MP, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P],
+    "gym_mpc_gains_all": [_MP, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _D, _P, _P, _P, _P],
+    "gym_mpc_box_workspace": [_I64, _I32, _I32, C.POINTER(C.c_int64)],
+    "gym_mpc_box_qp": [_P, _P, _P, _I32, _P, _P, _P, _P, _I64, _I32, _D, _I32, _P, _I64, _P, _P, _P, _P, _P],
+    "gym_mpc_box_rollout": [_MP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _P, _I64, _P, _P, _P,
+                            _P, _P],
     "gym_timing_create": [C.POINTER(GymTiming)],
     "gym_timing_destroy": [C.POINTER(GymTiming)],
     "gym_timing_collect": [C.POINTER(GymTiming)],

@@ -417,3 +417,90 @@ class AcrobotEngine:
                                                  _lib.TRACK_SINGLE if single else 0, x.data_ptr(), u.data_ptr(),
                                                  self.stream), "gym_track_rollout_ex")
         return x, u
+
+    # ------------------------------------------------------------- torque-limited MPC (box QP)
+    def mpc_gains_all(self, x_ref, u_ref, x_f, u_f, Q, R, L: int, nwin: int, max_iter: int = 1000,
+                      tol: float = 1e-6):
+        """gym_mpc_gains_all: mpc_gains with every stage's gain of every window.  Returns device tensors
+        (K_all (nwin,L-1,2,4), Q_T (4,4), iterations (1,) int32); K_all[:, 0] is mpc_gains' K0 bit for bit."""
+        x_ref = self.t(x_ref).reshape(-1, 4); u_ref = self.t(u_ref).reshape(-1, 2)
+        x_f = self.t(x_f).reshape(4); u_f = self.t(u_f).reshape(2)
+        S = x_ref.shape[0] - 1
+        if u_ref.shape[0] < S:
+            raise ValueError(f"u_ref must hold {S} stages, got {u_ref.shape[0]}")
+        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        K = torch.empty((nwin, int(L) - 1, 2, 4), dtype=F64, device=self.device)
+        P = torch.empty((4, 4), dtype=F64, device=self.device)
+        it = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gym_mpc_gains_all(C.byref(self.model), x_ref.data_ptr(), u_ref.data_ptr(), S,
+                                              x_f.data_ptr(), u_f.data_ptr(), Qh.ctypes.data, Rh.ctypes.data, int(L),
+                                              int(nwin), int(max_iter), float(tol), K.data_ptr(), P.data_ptr(),
+                                              it.data_ptr(), self.stream), "gym_mpc_gains_all")
+        return K, P, it
+
+    def mpc_box_workspace(self, B: int, L: int, rows: int) -> torch.Tensor:
+        """The caller-owned workspace of gym_mpc_box_qp (rows = stages given) / gym_mpc_box_rollout (rows = N)."""
+        need = C.c_int64()
+        _lib.check(self.lib.gym_mpc_box_workspace(int(B), int(L), int(rows), C.byref(need)), "gym_mpc_box_workspace")
+        return torch.empty(need.value, dtype=torch.uint8, device=self.device)
+
+    def mpc_box_qp(self, A, Bm, u_ref, Q, R, QT, x0, L: int, tau_max: float, max_qp_iters: int = 32, ws=None):
+        """gym_mpc_box_qp: the torque-limited QP of one window for a batch x0 (B,4).  Stages A (S,4,4), Bm (S,4,2),
+        u_ref (S,2) are host arrays (S >= L-1).  Returns device tensors U (B,L-1,2), X (B,L,4), iterations (B,)
+        int32, converged (B,) int32."""
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64)).reshape(-1, 4, 4)
+        Bm = np.ascontiguousarray(np.asarray(Bm, dtype=np.float64)).reshape(-1, 4, 2)
+        ur = np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64)).reshape(-1, 2)
+        S, L = A.shape[0], int(L)
+        if Bm.shape[0] != S or ur.shape[0] < S or S < L - 1:
+            raise ValueError(f"a window of {L} stages needs {L - 1} rows of A, B and u_ref, got {S} / {Bm.shape[0]} / "
+                             f"{ur.shape[0]}")
+        ur = np.ascontiguousarray(ur[:S])
+        if np.any(Bm[:, :, 0] != 0.0):
+            raise ValueError("the torque-limited QP needs B[:, 0] = 0 at every stage (channel 0 must separate)")
+        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
+            raise ValueError(f"the torque-limited QP needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
+        QTd = self.t(QT).reshape(4, 4)
+        x0 = self.t(x0).reshape(-1, 4)
+        B = x0.shape[0]
+        ws = self.mpc_box_workspace(B, L, S) if ws is None else ws
+        U = torch.empty((B, L - 1, 2), dtype=F64, device=self.device)
+        X = torch.empty((B, L, 4), dtype=F64, device=self.device)
+        it = torch.empty(B, dtype=torch.int32, device=self.device)
+        conv = torch.empty(B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gym_mpc_box_qp(A.ctypes.data, Bm.ctypes.data, ur.ctypes.data, S, Qh.ctypes.data,
+                                           Rh.ctypes.data, QTd.data_ptr(), x0.data_ptr(), B, L, float(tau_max),
+                                           int(max_qp_iters), ws.data_ptr(), ws.numel(), U.data_ptr(), X.data_ptr(),
+                                           it.data_ptr(), conv.data_ptr(), self.stream), "gym_mpc_box_qp")
+        return U, X, it, conv
+
+    def mpc_box_rollout(self, x0, x_ref, u_ref, x_f, u_f, Q, R, QT, K_all, tau_max: float, max_qp_iters: int = 32,
+                        ws=None):
+        """gym_mpc_box_rollout: the torque-limited closed loop of B lanes.  Returns device tensors x (B,N,4),
+        u (B,N-1,2), qp_iters (B,N-1) int32, unconverged (B,) int32."""
+        x0 = self.t(x0).reshape(-1, 4)
+        x_ref = self.t(x_ref).reshape(-1, 4); u_ref = self.t(u_ref).reshape(-1, 2)
+        x_f = self.t(x_f).reshape(4); u_f = self.t(u_f).reshape(2)
+        QTd = self.t(QT).reshape(4, 4)
+        N = x_ref.shape[0]
+        K_all = self.t(K_all)
+        if K_all.ndim != 4 or K_all.shape[0] != N - 1 or K_all.shape[2:] != (2, 4):
+            raise ValueError(f"K_all must be ({N - 1}, L-1, 2, 4), got {tuple(K_all.shape)}")
+        if u_ref.shape[0] < N - 1:
+            raise ValueError(f"u_ref must hold {N - 1} stages, got {u_ref.shape[0]}")
+        L = K_all.shape[1] + 1
+        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        B = x0.shape[0]
+        ws = self.mpc_box_workspace(B, L, N) if ws is None else ws
+        x = torch.empty((B, N, 4), dtype=F64, device=self.device)
+        u = torch.empty((B, N - 1, 2), dtype=F64, device=self.device)
+        it = torch.empty((B, N - 1), dtype=torch.int32, device=self.device)
+        unconv = torch.empty(B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gym_mpc_box_rollout(C.byref(self.model), x0.data_ptr(), x_ref.data_ptr(),
+                                                u_ref.data_ptr(), x_f.data_ptr(), u_f.data_ptr(), Qh.ctypes.data,
+                                                Rh.ctypes.data, QTd.data_ptr(), K_all.data_ptr(), B, N, L,
+                                                float(tau_max), int(max_qp_iters), ws.data_ptr(), ws.numel(),
+                                                x.data_ptr(), u.data_ptr(), it.data_ptr(), unconv.data_ptr(),
+                                                self.stream), "gym_mpc_box_rollout")
+        return x, u, it, unconv

@@ -4,16 +4,25 @@ Reference: /root/reference/trajectory_tracking.py (main.py task_3 / task_4).  Sa
 return values; the arithmetic runs in the gfx950 kernels of csrc/tracking_kernels.hip (gym_tv_lqr_gains,
 gym_dare_fixed_point, gym_lq_forward, gym_track_rollout) and the acrobot kernels (Jacobians, RK4).
 
-The MPC QP (solver_mpc :73-140) has only equality constraints (test_constraints = False, :87), so its
-solution is the finite-horizon LQ solution over the window; it is computed exactly (no IPOPT iterations):
-u0 = K_0(t) x0 with K_0(t) the window's first gain.  Every lane follows the same reference, so the gains of
-all T control steps are computed once (one window per thread) and the B perturbed initial states are then
-simulated in closed loop in one batched kernel -- the same controls the per-step re-solve produces.
+Without a torque limit (the reference's default, test_constraints = False, :87) the MPC QP (solver_mpc
+:73-140) has only equality constraints, so its solution is the finite-horizon LQ solution over the window; it
+is computed exactly (no IPOPT iterations): u0 = K_0(t) x0 with K_0(t) the window's first gain.  Every lane
+follows the same reference, so the gains of all T control steps are computed once (one window per thread) and
+the B perturbed initial states are then simulated in closed loop in one batched kernel -- the same controls
+the per-step re-solve produces.
 
-Batched additions: ``LQR_tracking_batch`` and ``solve_mpc_tracking_batch`` take x0 (B,4) and return device
-tensors.  There is no CPU fallback.
+With ``tau_max`` (the reference's test_constraints path, :87-114, tau_max = 18) every stage of the window obeys
+-tau_max <= u_t + u_ref_t <= tau_max, and each lane at each control step owns an inequality-constrained QP.  It
+is solved exactly by a primal-dual active set over a clamped Riccati sweep (gym_mpc_box_qp /
+gym_mpc_box_rollout; DESIGN "Torque-limited MPC"), at most ``max_qp_iters`` sweeps per QP; a QP that has not
+settled by then returns the clipped last iterate and is counted in ``unconverged``.
+
+Batched additions: ``LQR_tracking_batch``, ``solve_mpc_tracking_batch`` and ``solve_mpc_tracking_box_batch``
+take x0 (B,4) and return device tensors.  There is no CPU fallback.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -30,6 +39,7 @@ R_MPC = np.diag([1e-6, 10.0])                       # :37
 X_F = np.array([np.pi, 0.0, 0.0, 0.0])              # :31
 U_F = np.array([0.0, 0.0])                          # :32
 T_PRED = 75                                         # :10
+TAU_MAX = 18.0                                      # :91 (solver_mpc's torque limit, test_constraints)
 MPC_FUSED_MAX_STAGES = 256                          # gym_mpc_gains: T_pred + 2 stages per workgroup's LDS table
 
 
@@ -137,23 +147,82 @@ def solve_mpc_tracking_batch(x0, x_ref, u_ref, T_pred: int = T_PRED):
     return x, u, K0
 
 
-def solve_mpc_tracking(x0, x_ref, u_ref, T, T_pred: int = T_PRED):
-    """trajectory_tracking.py:8-69 -> (x_real (N,4), u_real (N-1,2)); control steps t < T-1."""
+@dataclass
+class MpcBoxResult:
+    """solve_mpc_tracking_box_batch's result (device tensors): x (B,N,4), u (B,N-1,2), K0 (N-1,2,4) the
+    unconstrained first gains, qp_iters (B,N-1) int32 active-set sweeps per QP, unconverged (B,) int32 QPs per lane
+    that reached max_qp_iters without settling."""
+    x: torch.Tensor
+    u: torch.Tensor
+    K0: torch.Tensor
+    qp_iters: torch.Tensor
+    unconverged: torch.Tensor
+
+
+def _check_box(tau_max, T_pred, max_qp_iters):
+    if not (np.isfinite(tau_max) and tau_max > 0):
+        raise ValueError(f"tau_max must be finite and positive, got {tau_max}")
+    if int(T_pred) < 2 or int(T_pred) + 2 > MPC_FUSED_MAX_STAGES:
+        raise ValueError(f"T_pred must be in [2, {MPC_FUSED_MAX_STAGES - 2}] for the torque-limited QP, got {T_pred}")
+    if int(max_qp_iters) < 1:
+        raise ValueError(f"max_qp_iters must be at least 1, got {max_qp_iters}")
+
+
+def solve_mpc_tracking_box_batch(x0, x_ref, u_ref, tau_max: float = TAU_MAX, T_pred: int = T_PRED,
+                                 max_qp_iters: int = 32, Q=Q_MPC, R=R_MPC) -> MpcBoxResult:
+    """Batched receding-horizon MPC with the torque limit |u_ref + u| <= tau_max on every stage of every window
+    (solve_mpc_tracking :8-69 with solver_mpc's test_constraints on): x0 (B,4) -> MpcBoxResult."""
+    _check_box(tau_max, T_pred, max_qp_iters)
+    eng = _eng()
+    x_ref = eng.t(x_ref).reshape(-1, 4)
+    u_ref = eng.t(u_ref).reshape(-1, 2)
+    x_f, u_f = _final_state(eng)
+    K_all, QT, _ = eng.mpc_gains_all(x_ref, u_ref, x_f, u_f, Q, R, L=int(T_pred), nwin=x_ref.shape[0] - 1)
+    x, u, it, unconv = eng.mpc_box_rollout(x0, x_ref, u_ref, x_f, u_f, Q, R, QT, K_all, float(tau_max),
+                                           int(max_qp_iters))
+    return MpcBoxResult(x, u, K_all[:, 0].contiguous(), it, unconv)
+
+
+def solve_mpc_tracking(x0, x_ref, u_ref, T, T_pred: int = T_PRED, tau_max=None):
+    """trajectory_tracking.py:8-69 -> (x_real (N,4), u_real (N-1,2)); control steps t < T-1.  tau_max: the torque
+    limit of solver_mpc's test_constraints path (None: the reference's default, no limit)."""
     x_ref = np.asarray(x_ref, dtype=float)
     u_ref = np.asarray(u_ref, dtype=float)
     steps = int(T) - 1
     x_real = np.zeros(x_ref.shape)
     u_real = np.zeros(u_ref.shape)
+    if tau_max is not None:
+        res = solve_mpc_tracking_box_batch(np.asarray(x0, dtype=float).reshape(1, 4), x_ref, u_ref, tau_max, T_pred)
+        x_real[:steps + 1] = _np(res.x[0])[:steps + 1]
+        u_real[:steps] = _np(res.u[0])[:steps]
+        return x_real, u_real
     x, u, _ = solve_mpc_tracking_batch(np.asarray(x0, dtype=float).reshape(1, 4), x_ref, u_ref, T_pred)
     x_real[:steps + 1] = _np(x[0])[:steps + 1]
     u_real[:steps] = _np(u[0])[:steps]
     return x_real, u_real
 
 
-def solver_mpc(x0, A_list, B_list, Q, R, Q_T, T_pred, u_ref=None):
+def solver_mpc(x0, A_list, B_list, Q, R, Q_T, T_pred, u_ref=None, tau_max=None):
     """trajectory_tracking.py:73-140: the window's QP solved exactly -> (U0 (2,), X_opt (T_pred,4),
-    U_opt (T_pred,2)); U_opt's last row (no cost, no constraint in the reference's QP) is 0."""
+    U_opt (T_pred,2)); U_opt's last row (no cost, no constraint in the reference's QP) is 0.  tau_max: the torque
+    limit -tau_max <= u_t + u_ref_t <= tau_max of the test_constraints path (:87-114; needs u_ref, as the reference
+    does); None: no limit."""
     eng = _eng()
+    if tau_max is not None:
+        if u_ref is None:
+            raise ValueError("solver_mpc needs u_ref to apply tau_max (the limit is on u_t + u_ref_t)")
+        _check_box(tau_max, T_pred, 32)
+        Lw = int(T_pred)
+        A = np.asarray(A_list[:Lw - 1], dtype=float).reshape(-1, 4, 4)
+        B = np.asarray(B_list[:Lw - 1], dtype=float).reshape(-1, 4, 2)
+        ur = np.asarray(u_ref, dtype=float).reshape(-1, 2)[:Lw - 1]
+        U, X, _, conv = eng.mpc_box_qp(A, B, ur, Q, R, Q_T, np.asarray(x0, dtype=float).reshape(1, 4), Lw,
+                                       float(tau_max))
+        if not int(conv[0].item()):
+            print("Attention! mpc solver did not settle its active set: clipped last iterate returned")
+        U_opt = np.zeros((Lw, 2))
+        U_opt[:-1] = _np(U[0])
+        return U_opt[0].copy(), _np(X[0]), U_opt
     A = eng.t(np.asarray(A_list[:T_pred], dtype=float)).reshape(-1, 4, 4)
     B = eng.t(np.asarray(B_list[:T_pred], dtype=float)).reshape(-1, 4, 2)
     K = eng.tv_lqr_gains(A, B, Q, R, Q_T, L=int(T_pred), nwin=1, all_gains=True,

@@ -386,6 +386,44 @@ int gym_track_rollout_ex(const gym_model* m, const double* x0, const double* x_f
                          const double* K, int64_t B, int32_t N, int32_t flags, double* x_out, double* u_out,
                          void* stream);
 
+/* ---------------- Torque-limited MPC: the window QP with -tau_max <= u_t + u_ref_t <= tau_max ----------------
+ * (solver_mpc with test_constraints on, trajectory_tracking.py:87-114).  B_d's column 0 is zero for the acrobot, so
+ * channel 0 is u_t[0] = clip(0, lo_t, hi_t) and channel 1 a scalar-input LQ problem with a box, solved per lane by a
+ * primal-dual active set over a clamped Riccati sweep.  A QP whose sweep count reaches max_qp_iters is UNCONVERGED
+ * (iterations == max_qp_iters exactly then): it returns clip(u, lo, hi) of its last iterate and is flagged, never an
+ * error; a converged QP settled its active set in fewer sweeps and its u is the exact minimiser.
+ * R must be diagonal with R[1][1] > 0, tau_max finite and positive, 2 <= L <= 254 (GYM_EINVAL otherwise).
+ * Additive to ABI 18: no existing entry point or structure changed. */
+/* gym_mpc_gains with every stage's gain of every window: K_all (nwin, L-1, 2, 4); K_all[w][0] is gym_mpc_gains'
+ * K_out[w] bit for bit (the same recursion).  The QP's first iterate (no bound active) for all lanes. */
+int gym_mpc_gains_all(const gym_model* m, const double* x_ref, const double* u_ref, int32_t S, const double* x_f,
+                      const double* u_f, const double Q[16], const double R[4], int32_t L, int32_t nwin,
+                      int32_t max_iter, double tol, double* K_all, double* QT_out, int32_t* iters_out, void* stream);
+/* [host] bytes of the workspace of B lanes, windows of L stages and a stage table of `rows` rows (gym_mpc_box_qp:
+ * rows = S; gym_mpc_box_rollout: rows = N).  The table and, per lane, (k, d, x, u) of every stage and the stage
+ * states, lane-fastest. */
+int gym_mpc_box_workspace(int64_t B, int32_t L, int32_t rows, int64_t* bytes_out);
+/* A batch of QPs on one window (solver_mpc and the tests).  Stages A (S,4,4), B (S,4,2), u_ref (S,2) [HOST, as the
+ * reference's lists; S >= L-1; read by stream-ordered copies into the workspace, so pinned arrays must stay
+ * unchanged until the stream has passed them]; B[:, :, 0] != 0 anywhere: GYM_EINVAL.  Q, R [host]; QT (4,4), x0
+ * (B,4) [device].  Outputs [device]: U (B,L-1,2), X (B,L,4) (an unconverged QP: the last iterate's states),
+ * iters_out (B), converged_out (B). */
+int gym_mpc_box_qp(const double* A, const double* B_stage, const double* u_ref, int32_t S, const double Q[16],
+                   const double R[4], const double* QT, const double* x0, int64_t B, int32_t L, double tau_max,
+                   int32_t max_qp_iters, void* ws, int64_t ws_bytes, double* U, double* X, int32_t* iters_out,
+                   int32_t* converged_out, void* stream);
+/* The torque-limited closed loop (solve_mpc_tracking :43-67), one trajectory per lane: per control step s,
+ * e = x - x_ref[s], the QP of window s (stages s .. s+L-2 of the reference's linearisation, the pad (x_f, u_f) past
+ * its end, first iterate from K_all[s]), u_real[s] = u_ref[s] + u_0 (a first control on its bound applies the limit
+ * itself), one RK4 step.  x_ref (N,4), u_ref (N-1,2), x_f (4), u_f (2), QT (4,4), K_all (N-1,L-1,2,4) of
+ * gym_mpc_gains_all, x0 (B,4) [device]; Q, R [host].  Outputs [device], lane-major: x_out (B,N,4), u_out (B,N-1,2),
+ * qp_iters_out (B,N-1), unconverged_out (B) = the lane's number of unconverged QPs. */
+int gym_mpc_box_rollout(const gym_model* m, const double* x0, const double* x_ref, const double* u_ref,
+                        const double* x_f, const double* u_f, const double Q[16], const double R[4], const double* QT,
+                        const double* K_all, int64_t B, int32_t N, int32_t L, double tau_max, int32_t max_qp_iters,
+                        void* ws, int64_t ws_bytes, double* x_out, double* u_out, int32_t* qp_iters_out,
+                        int32_t* unconverged_out, void* stream);
+
 /* [host] create / destroy the events of a gym_timing; collect = add the elapsed time of every pending
  * pair (call only after the stream that recorded them has been synchronised). */
 int gym_timing_create(gym_timing* t);
