@@ -600,7 +600,7 @@ class BatchedNewtonSolver:
 
     def phase_kind(self) -> str | None:
         """The build of the phase kernel this batch's full phases launch (pipelined schedule; gym_newton_phase_kind):
-        "two-wavefront" (more than 7/8 and at most two wavefronts per SIMD: compiled for two, prefetching two stages
+        "two-wavefront" (more than 7/4 and at most 2 wavefronts per SIMD: compiled for two, prefetching two stages
         ahead) or "four-wavefront"; None for the other schedules.  Both builds give the same bits."""
         if self.schedule != "pipelined":
             return None

@@ -97,7 +97,7 @@ def test_cfg4_rank_share_and_pooled_resolve():
 
 def test_two_wavefront_phase_kernel_is_bitwise_the_four_wavefront_one():
     """gym_newton_phase picks its two-wavefront build (compiled for two wavefronts per SIMD, both stage loops
-    prefetching two stages ahead) for batches of more than 7/8 and at most two wavefronts per SIMD, e.g. the
+    prefetching two stages ahead) for batches of more than 7/4 and at most 2 wavefronts per SIMD, e.g. the
     131,072 lanes of one rank's cfg 4 share, and its four-wavefront build for the headline 262,144.  Same arithmetic
     in the same order: lanes [0, 131072) of a 262,144-lane solve and 131,072-lane solves on each instantiation of the
     two-wavefront build (shared references with the tau1 planes skipped, the general kernels that stream them, and
