@@ -10,6 +10,7 @@
 // The batched part is the closed-loop RK4 simulation of B perturbed initial states under the shared
 // feed-forward / feedback sequence (simulate_tracking :206-216 and the MPC loop :43-60), one lane per thread
 // with the gains, reference and feed-forward read through wave-uniform (scalar) loads.
+// Per-lane LQR tracking (every lane follows its OWN trajectory, so the gains are per-lane streams) is lqr_lanes.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -984,6 +985,8 @@ inline bool box_weights_ok(const double* R) {   // the channel split needs a dia
     return R[1] == 0.0 && R[2] == 0.0 && R[3] > 0.0 && R[3] <= 1.7976931348623157e308;
 }
 
+#include "lqr_lanes.hpp"   // per-lane LQR tracking: every lane follows its own trajectory
+
 inline M44 m44(const double* p) { M44 m; for (int i = 0; i < 16; ++i) m.v[i] = p[i]; return m; }
 inline M22 m22(const double* p) { M22 m; for (int i = 0; i < 4; ++i) m.v[i] = p[i]; return m; }
 inline int launch_status() { return (int)hipGetLastError(); }
@@ -1119,6 +1122,69 @@ int gym_track_rollout_ex(const gym_model* m, const double* x0, const double* x_f
 int gym_track_rollout(const gym_model* m, const double* x0, const double* x_ff, const double* u_ff, const double* K,
                       int64_t B, int32_t N, double* x_out, double* u_out, void* s) {
     return gym_track_rollout_ex(m, x0, x_ff, u_ff, K, B, N, 0, x_out, u_out, s);
+}
+
+// ---- per-lane LQR tracking (lqr_lanes.hpp) ----
+static bool lanes_sizes_ok(int64_t B, int32_t N) {
+    return B >= 1 && N >= 2 && (B + 63) / 64 * 64 <= GYM_MAX_BP;
+}
+
+int gym_lqr_lanes_workspace(int64_t B, int32_t N, int64_t* bytes_out) {
+    if (!bytes_out || !lanes_sizes_ok(B, N)) return GYM_EINVAL;
+    *bytes_out = lanes_layout(B, N).bytes;
+    return 0;
+}
+
+// solve_LQR_tracking (trajectory_tracking.py:170-203) per lane
+int gym_lqr_lanes_gains(const gym_model* m, const double* x_opt, const double* u_opt, int64_t B, int32_t N,
+                        const double Q[16], const double R[4], const double QT[16], void* ws, int64_t ws_bytes,
+                        double* K_out, void* s) {
+    if (!m || !x_opt || !u_opt || !Q || !R || !QT || !ws || !lanes_sizes_ok(B, N) || !box_weights_ok(R) ||
+        !lanes_sym(Q) || !lanes_sym(QT))
+        return GYM_EINVAL;
+    const LanesLayout lo = lanes_layout(B, N);
+    const int T = N - 1;
+    const int64_t groups = lo.Bp / BLK;
+    const int ntx = (N + 15) / 16, ntu = (T + 31) / 32, ntk = (T + 15) / 16;
+    if (ws_bytes < lo.bytes || groups * ntx > ((int64_t)1 << 31) - 1) return GYM_EINVAL;
+    char* base = static_cast<char*>(ws);
+    double2* xs = reinterpret_cast<double2*>(base);
+    double* us = reinterpret_cast<double*>(base + lo.off_u);
+    double2* ks = reinterpret_cast<double2*>(base + lo.off_k);
+    hipStream_t st = (hipStream_t)s;
+    hipLaunchKernelGGL(k_lqr_pack<4>, dim3((unsigned)(groups * ntx)), dim3(LL_THREADS), 0, st,
+                       reinterpret_cast<const double2*>(x_opt), reinterpret_cast<double*>(xs), B, lo.Bp, (int)N, ntx);
+    hipLaunchKernelGGL(k_lqr_pack<2>, dim3((unsigned)(groups * ntu)), dim3(LL_THREADS), 0, st,
+                       reinterpret_cast<const double2*>(u_opt), us, B, lo.Bp, T, ntu);
+    hipLaunchKernelGGL(k_lqr_lane_gains, dim3((unsigned)groups), dim3(BLK), 0, st, Dyn(*m), sym4(Q), sym4(QT), R[3], xs,
+                       us, ks, lo.Bp, (int)N);
+    if (K_out)
+        hipLaunchKernelGGL(k_lqr_unpack_gains, dim3((unsigned)(groups * ntk)), dim3(LL_THREADS), 0, st, ks,
+                           reinterpret_cast<double2*>(K_out), B, lo.Bp, T, ntk);
+    return launch_status();
+}
+
+// simulate_tracking (trajectory_tracking.py:206-216) per lane and perturbed start
+int gym_lqr_lanes_rollout(const gym_model* m, const double* x0, int64_t B, int32_t P, int32_t N, const void* ws,
+                          int64_t ws_bytes, double* x_out, double* u_out, double* summary_out, void* s) {
+    if (!m || !x0 || !ws || !summary_out || !lanes_sizes_ok(B, N) || P < 1 || B > GYM_MAX_BP / P ||
+        (x_out == nullptr) != (u_out == nullptr))
+        return GYM_EINVAL;
+    const LanesLayout lo = lanes_layout(B, N);
+    if (ws_bytes < lo.bytes) return GYM_EINVAL;
+    const char* base = static_cast<const char*>(ws);
+    const double2* xs = reinterpret_cast<const double2*>(base);
+    const double* us = reinterpret_cast<const double*>(base + lo.off_u);
+    const double2* ks = reinterpret_cast<const double2*>(base + lo.off_k);
+    const int64_t nb = (lo.Bp / BLK) * P;                  // <= 2^20 + 2^26 / 64: far below the grid limit
+    const dim3 grid((unsigned)((nb + 7) / 8 * 8));
+    if (x_out)
+        hipLaunchKernelGGL(k_lqr_lane_rollout<true>, grid, dim3(BLK), 0, (hipStream_t)s, Dyn(*m), x0, xs, us, ks, B,
+                           lo.Bp, (int)P, (int)N, x_out, u_out, summary_out);
+    else
+        hipLaunchKernelGGL(k_lqr_lane_rollout<false>, grid, dim3(BLK), 0, (hipStream_t)s, Dyn(*m), x0, xs, us, ks, B,
+                           lo.Bp, (int)P, (int)N, x_out, u_out, summary_out);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -504,3 +504,47 @@ class AcrobotEngine:
                                                 x.data_ptr(), u.data_ptr(), it.data_ptr(), unconv.data_ptr(),
                                                 self.stream), "gym_mpc_box_rollout")
         return x, u, it, unconv
+
+    # ------------------------------------------------------------- per-lane LQR tracking
+    def lqr_lanes_workspace(self, B: int, N: int) -> torch.Tensor:
+        """The caller-owned workspace of gym_lqr_lanes_gains / gym_lqr_lanes_rollout for B lanes of N knots."""
+        need = C.c_int64()
+        _lib.check(self.lib.gym_lqr_lanes_workspace(int(B), int(N), C.byref(need)), "gym_lqr_lanes_workspace")
+        return torch.empty(need.value, dtype=torch.uint8, device=self.device)
+
+    def lqr_lanes_gains(self, x_opt, u_opt, Q, R, QT, gains: bool = True, ws=None):
+        """gym_lqr_lanes_gains: solve_LQR_tracking per lane along x_opt (B,N,4), u_opt (B,N-1,2).  Returns (ws, K):
+        the filled workspace lqr_lanes_rollout takes, and K (B,N-1,2,4) on the device (None unless ``gains``)."""
+        x_opt = self.t(x_opt); u_opt = self.t(u_opt)
+        if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
+            raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
+        B, N = x_opt.shape[0], x_opt.shape[1]
+        if tuple(u_opt.shape) != (B, N - 1, 2):
+            raise ValueError(f"u_opt must be ({B},{N - 1},2) for x_opt {tuple(x_opt.shape)}, got {tuple(u_opt.shape)}")
+        Qh, Rh, QTh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R"), self._host_mat(QT, 4, "QT")
+        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
+            raise ValueError(f"per-lane LQR tracking needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
+        for name, M in (("Q", Qh), ("QT", QTh)):
+            if not np.array_equal(M, M.T):
+                raise ValueError(f"{name} must be symmetric, got {M.tolist()}")
+        ws = self.lqr_lanes_workspace(B, N) if ws is None else ws
+        K = torch.empty((B, N - 1, 2, 4), dtype=F64, device=self.device) if gains else None
+        _lib.check(self.lib.gym_lqr_lanes_gains(C.byref(self.model), x_opt.data_ptr(), u_opt.data_ptr(), B, N,
+                                                Qh.ctypes.data, Rh.ctypes.data, QTh.ctypes.data, ws.data_ptr(),
+                                                ws.numel(), _lib.ptr(K), self.stream), "gym_lqr_lanes_gains")
+        return ws, K
+
+    def lqr_lanes_rollout(self, ws, x0, N: int, trajectories: bool = True):
+        """gym_lqr_lanes_rollout on a workspace lqr_lanes_gains filled: x0 (B,P,4) -> (x (B,P,N,4), u (B,P,N-1,2),
+        summary (3,B,P) = err_final, err_max, u_max) on the device; x, u are None unless ``trajectories``."""
+        x0 = self.t(x0)
+        if x0.ndim != 3 or x0.shape[2] != 4 or x0.shape[0] < 1 or x0.shape[1] < 1:
+            raise ValueError(f"x0 must be (B,P,4), got {tuple(x0.shape)}")
+        B, P, N = x0.shape[0], x0.shape[1], int(N)
+        x = torch.empty((B, P, N, 4), dtype=F64, device=self.device) if trajectories else None
+        u = torch.empty((B, P, N - 1, 2), dtype=F64, device=self.device) if trajectories else None
+        summary = torch.empty((3, B, P), dtype=F64, device=self.device)
+        _lib.check(self.lib.gym_lqr_lanes_rollout(C.byref(self.model), x0.data_ptr(), B, P, N, ws.data_ptr(),
+                                                  ws.numel(), _lib.ptr(x), _lib.ptr(u), summary.data_ptr(),
+                                                  self.stream), "gym_lqr_lanes_rollout")
+        return x, u, summary

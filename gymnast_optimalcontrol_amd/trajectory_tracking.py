@@ -18,7 +18,10 @@ gym_mpc_box_rollout; DESIGN "Torque-limited MPC"), at most ``max_qp_iters`` swee
 settled by then returns the clipped last iterate and is counted in ``unconverged``.
 
 Batched additions: ``LQR_tracking_batch``, ``solve_mpc_tracking_batch`` and ``solve_mpc_tracking_box_batch``
-take x0 (B,4) and return device tensors.  There is no CPU fallback.
+take x0 (B,4) and return device tensors; they follow one reference shared by every lane.  ``LQR_tracking_lanes`` /
+``lqr_gains_lanes`` track every lane's own trajectory (x_opt (B,N,4), u_opt (B,N-1,2), e.g. a batched solve's result):
+per-lane gains and closed-loop rollouts in the kernels of csrc/lqr_lanes.hpp (gym_lqr_lanes_gains /
+gym_lqr_lanes_rollout).  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -116,6 +119,63 @@ def LQR_tracking_batch(x_ref, u_ref, x0):
     K = lqr_gains(x_ref, u_ref)
     x, u = eng.track_rollout(x0, x_ref, u_ref, K)
     return x, u, K
+
+
+@dataclass
+class LqrLanesResult:
+    """LQR_tracking_lanes' result (device tensors; a field not asked for is None).  With x0 (B,4): x (B,N,4),
+    u (B,N-1,2), summaries (B,); with x0 (B,P,4): x (B,P,N,4), u (B,P,N-1,2), summaries (B,P).  K (B,N-1,2,4).
+    err_final = |x_{N-1} - x_opt_{N-1}|_inf, err_max = max_t |x_t - x_opt_t|_inf, u_max = max_t |u_t[1]|."""
+    x: torch.Tensor | None
+    u: torch.Tensor | None
+    K: torch.Tensor | None
+    err_final: torch.Tensor
+    err_max: torch.Tensor
+    u_max: torch.Tensor
+
+
+def _lane_trajectories(eng, x_opt, u_opt):
+    """(x_opt (B,N,4), u_opt (B,N-1,2)) on the device; u_opt with N rows is trimmed as newton_Algorithm trims u_ref
+    (trajectory_generation.py:301-303), other mismatches raise."""
+    x_opt = eng.t(x_opt)
+    u_opt = eng.t(u_opt)
+    if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
+        raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
+    B, N = x_opt.shape[0], x_opt.shape[1]
+    if u_opt.ndim != 3 or u_opt.shape[2] != 2 or u_opt.shape[0] != B or u_opt.shape[1] not in (N - 1, N):
+        raise ValueError(f"u_opt must be ({B},{N - 1},2) (or {N} rows) for x_opt {tuple(x_opt.shape)}, "
+                         f"got {tuple(u_opt.shape)}")
+    if u_opt.shape[1] == N:
+        u_opt = u_opt[:, :N - 1].contiguous()
+    return x_opt, u_opt
+
+
+def lqr_gains_lanes(x_opt, u_opt, Q=Q_REG, R=R_REG, QT=QT_REG) -> torch.Tensor:
+    """solve_LQR_tracking (:170-203) per lane: x_opt (B,N,4), u_opt (B,N-1,2) -> K (B,N-1,2,4) on the device
+    (row 0 of every gain is exactly zero: tau1 is unactuated)."""
+    eng = _eng()
+    x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
+    return eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=True)[1]
+
+
+def LQR_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bool = True, Q=Q_REG, R=R_REG,
+                       QT=QT_REG) -> LqrLanesResult:
+    """LQR tracking of every lane's OWN trajectory (main.py task_2's result into task_3, per lane): lane b's gains
+    come from (x_opt[b], u_opt[b]) and its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are
+    simulated in closed loop against them.  ``trajectories=False`` returns only the summaries (a Monte-Carlo run has
+    no use for B P trajectories), ``gains=False`` skips the lane-major copy of K."""
+    eng = _eng()
+    x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
+    B, N = x_opt.shape[0], x_opt.shape[1]
+    x0 = eng.t(x0)
+    flat = x0.ndim == 2
+    if x0.ndim not in (2, 3) or x0.shape[-1] != 4 or x0.shape[0] != B or (x0.ndim == 3 and x0.shape[1] < 1):
+        raise ValueError(f"x0 must be ({B},4) or ({B},P,4) for x_opt {tuple(x_opt.shape)}, got {tuple(x0.shape)}")
+    ws, K = eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=gains)
+    x, u, s = eng.lqr_lanes_rollout(ws, x0.reshape(B, -1, 4), N, trajectories=trajectories)
+    if flat:
+        x, u, s = (None if x is None else x[:, 0]), (None if u is None else u[:, 0]), s[:, :, 0]
+    return LqrLanesResult(x, u, K, s[0], s[1], s[2])
 
 
 def mpc_gains(x_ref, u_ref, T_pred: int = T_PRED, Q=Q_MPC, R=R_MPC, n_steps: int | None = None):

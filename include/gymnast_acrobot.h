@@ -424,6 +424,30 @@ int gym_mpc_box_rollout(const gym_model* m, const double* x0, const double* x_re
                         void* ws, int64_t ws_bytes, double* x_out, double* u_out, int32_t* qp_iters_out,
                         int32_t* unconverged_out, void* stream);
 
+/* ---------------- Per-lane LQR tracking: every lane tracks its own trajectory ----------------
+ * (main.py task_2's result fed to task_3, per lane.)  x_opt (B,N,4) and u_opt (B,N-1,2) are the lane-major arrays a
+ * batched solve returns; lane l gets its own gain sequence and P perturbed starts.  Row 0 of every K_t is exactly
+ * zero (B_d's column 0 is zero and R is diagonal), so only row 1 is computed and kept.  The workspace holds the
+ * trajectories and row 1 of the gains in the SoA layouts above (x_opt pairs (N,Bp/64,2,64), u_opt planes (N-1,2,Bp),
+ * K1 pairs (N-1,Bp/64,2,64), Bp = B rounded up to 64, 16-byte aligned).  A lane's results depend on that lane's
+ * inputs only (not on B, P, its position, or whether trajectories are stored).
+ * GYM_EINVAL: N < 2, B < 1, P < 1, Bp > GYM_MAX_BP, B P > GYM_MAX_BP, R not diagonal or R[1][1] <= 0, Q or QT not
+ * symmetric, a required pointer NULL, exactly one of x_out / u_out, ws_bytes too small.
+ * Additive to ABI 18: no existing entry point or structure changed. */
+/* [host] bytes of the workspace for B lanes of N knots */
+int gym_lqr_lanes_workspace(int64_t B, int32_t N, int64_t* bytes_out);
+/* solve_LQR_tracking (trajectory_tracking.py:170-203) per lane.  x_opt (B,N,4), u_opt (B,N-1,2) [device, lane-major];
+ * Q, R, QT [host].  Fills the workspace (packed x_opt, u_opt, gain row 1).  K_out optional: (B,N-1,2,4), row 0 = 0. */
+int gym_lqr_lanes_gains(const gym_model* m, const double* x_opt, const double* u_opt, int64_t B, int32_t N,
+                        const double Q[16], const double R[4], const double QT[16], void* ws, int64_t ws_bytes,
+                        double* K_out, void* stream);
+/* simulate_tracking (trajectory_tracking.py:206-216) per lane on a workspace gym_lqr_lanes_gains filled: u_t =
+ * u_opt_t + K_t (x_t - x_opt_t) (channel 0 is u_opt_t[0] itself), x_{t+1} = RK4(x_t, u_t).  x0 (B,P,4) [device].
+ * x_out (B,P,N,4), u_out (B,P,N-1,2) optional (both or neither); summary_out (3,B,P) = err_final = |x_{N-1} -
+ * x_opt_{N-1}|_inf, err_max = max_t |x_t - x_opt_t|_inf, u_max = max_t |u_t[1]| (NaN-propagating). */
+int gym_lqr_lanes_rollout(const gym_model* m, const double* x0, int64_t B, int32_t P, int32_t N, const void* ws,
+                          int64_t ws_bytes, double* x_out, double* u_out, double* summary_out, void* stream);
+
 /* [host] create / destroy the events of a gym_timing; collect = add the elapsed time of every pending
  * pair (call only after the stream that recorded them has been synchronised). */
 int gym_timing_create(gym_timing* t);
