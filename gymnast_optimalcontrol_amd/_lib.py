@@ -30,6 +30,7 @@ EXPORTS = (
     "gym_tv_lqr_gains", "gym_dare_fixed_point", "gym_mpc_gains", "gym_lq_forward", "gym_track_rollout", "gym_track_rollout_ex",
     "gym_mpc_gains_all", "gym_mpc_box_workspace", "gym_mpc_box_qp", "gym_mpc_box_rollout",
     "gym_lqr_lanes_workspace", "gym_lqr_lanes_gains", "gym_lqr_lanes_rollout",
+    "gym_mpc_lanes_gains",
     "gym_timing_create", "gym_timing_destroy", "gym_timing_collect",
 )
 KERNEL_KINDS = ("backward", "trial", "candidates", "retry", "stats", "phase_odd", "phase_even", "sigma", "run",
@@ -37,6 +38,7 @@ KERNEL_KINDS = ("backward", "trial", "candidates", "retry", "stats", "phase_odd"
 
 ABI_VERSION = 18        # GYM_ABI_VERSION of the header this binding mirrors
 MAX_BP = 1 << 26         # GYM_MAX_BP
+MPC_MAX_STAGES = 256     # the MPC gain kernels' LDS stage table: T_pred + 2 <= 256 (kMpcMaxStages)
 FLAG_U0_ZERO = 1         # GYM_FLAG_U0_ZERO
 FLAG_X_CKPT = 2          # GYM_FLAG_X_CKPT
 FLAG_RUN_SINGLE = 4      # GYM_FLAG_RUN_SINGLE
@@ -131,6 +133,7 @@ _SIGS = {
     "gym_lqr_lanes_workspace": [_I64, _I32, C.POINTER(C.c_int64)],
     "gym_lqr_lanes_gains": [_MP, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _P, _P],
     "gym_lqr_lanes_rollout": [_MP, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P, _P],
+    "gym_mpc_lanes_gains": [_MP, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P],
     "gym_timing_create": [C.POINTER(GymTiming)],
     "gym_timing_destroy": [C.POINTER(GymTiming)],
     "gym_timing_collect": [C.POINTER(GymTiming)],

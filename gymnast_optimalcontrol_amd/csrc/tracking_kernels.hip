@@ -10,7 +10,8 @@
 // The batched part is the closed-loop RK4 simulation of B perturbed initial states under the shared
 // feed-forward / feedback sequence (simulate_tracking :206-216 and the MPC loop :43-60), one lane per thread
 // with the gains, reference and feed-forward read through wave-uniform (scalar) loads.
-// Per-lane LQR tracking (every lane follows its OWN trajectory, so the gains are per-lane streams) is lqr_lanes.hpp.
+// Per-lane LQR tracking (every lane follows its OWN trajectory, so the gains are per-lane streams) is lqr_lanes.hpp;
+// per-lane MPC tracking (every window of every lane has its own first gain) is mpc_lanes.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -986,6 +987,7 @@ inline bool box_weights_ok(const double* R) {   // the channel split needs a dia
 }
 
 #include "lqr_lanes.hpp"   // per-lane LQR tracking: every lane follows its own trajectory
+#include "mpc_lanes.hpp"   // per-lane MPC tracking: the first gain of every window of every lane
 
 inline M44 m44(const double* p) { M44 m; for (int i = 0; i < 16; ++i) m.v[i] = p[i]; return m; }
 inline M22 m22(const double* p) { M22 m; for (int i = 0; i < 4; ++i) m.v[i] = p[i]; return m; }
@@ -1184,6 +1186,40 @@ int gym_lqr_lanes_rollout(const gym_model* m, const double* x0, int64_t B, int32
     else
         hipLaunchKernelGGL(k_lqr_lane_rollout<false>, grid, dim3(BLK), 0, (hipStream_t)s, Dyn(*m), x0, xs, us, ks, B,
                            lo.Bp, (int)P, (int)N, x_out, u_out, summary_out);
+    return launch_status();
+}
+
+// ---- per-lane MPC tracking (mpc_lanes.hpp) ----
+// solve_mpc_tracking's gains (trajectory_tracking.py:8-69) per lane: fills a gym_lqr_lanes_rollout workspace
+int gym_mpc_lanes_gains(const gym_model* m, const double* x_opt, const double* u_opt, int64_t B, int32_t N, int32_t L,
+                        const double Q[16], const double R[4], const double* QT_dev, void* ws, int64_t ws_bytes,
+                        double* K_out, void* s) {
+    if (!m || !x_opt || !u_opt || !Q || !R || !QT_dev || !ws || !lanes_sizes_ok(B, N) || L < 2 ||
+        L + 2 > kMpcMaxStages || !box_weights_ok(R) || !lanes_sym(Q))
+        return GYM_EINVAL;
+    const LanesLayout lo = lanes_layout(B, N);
+    const int T = N - 1;
+    const int64_t groups = lo.Bp / BLK;
+    const int ntx = (N + 15) / 16, ntu = (T + 31) / 32, ntk = (T + 15) / 16;
+    const int64_t nwork = lo.Bp * ((T + ML_W - 1) / ML_W);   // (lane, window block) workgroups
+    const int64_t gmax = ((int64_t)1 << 31) - 8;
+    if (ws_bytes < lo.bytes || groups * ntx > gmax || nwork > gmax) return GYM_EINVAL;
+    char* base = static_cast<char*>(ws);
+    double2* xs = reinterpret_cast<double2*>(base);
+    double* us = reinterpret_cast<double*>(base + lo.off_u);
+    double2* ks = reinterpret_cast<double2*>(base + lo.off_k);
+    hipStream_t st = (hipStream_t)s;
+    hipLaunchKernelGGL(k_lqr_pack<4>, dim3((unsigned)(groups * ntx)), dim3(LL_THREADS), 0, st,
+                       reinterpret_cast<const double2*>(x_opt), reinterpret_cast<double*>(xs), B, lo.Bp, (int)N, ntx);
+    hipLaunchKernelGGL(k_lqr_pack<2>, dim3((unsigned)(groups * ntu)), dim3(LL_THREADS), 0, st,
+                       reinterpret_cast<const double2*>(u_opt), us, B, lo.Bp, T, ntu);
+    const size_t lds = sizeof(double) * ML_ROWS * (ML_W + L - 2);
+    hipLaunchKernelGGL(k_mpc_lane_gains<ML_W>, dim3((unsigned)((nwork + 7) / 8 * 8)), dim3(ML_W), lds, st, Dyn(*m),
+                       sym4(Q), QT_dev, R[3], reinterpret_cast<const double2*>(x_opt),
+                       reinterpret_cast<const double2*>(u_opt), ks, B, lo.Bp, (int)N, (int)L, nwork);
+    if (K_out)
+        hipLaunchKernelGGL(k_lqr_unpack_gains, dim3((unsigned)(groups * ntk)), dim3(LL_THREADS), 0, st, ks,
+                           reinterpret_cast<double2*>(K_out), B, lo.Bp, T, ntk);
     return launch_status();
 }
 

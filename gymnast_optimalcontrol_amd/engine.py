@@ -81,6 +81,7 @@ class AcrobotEngine:
                    "gym_model_from_params")
         self.weights = weights or Weights()
         self._w = self.weights.c_struct()
+        self.mpc_qt_cache = {}     # (Q, R) -> Q_T of per-lane MPC tracking; it depends on this engine's model and dt
 
     # -------------------------------------------------------------------------------- utils
     def t(self, a, shape=None) -> torch.Tensor:
@@ -548,3 +549,39 @@ class AcrobotEngine:
                                                   ws.numel(), _lib.ptr(x), _lib.ptr(u), summary.data_ptr(),
                                                   self.stream), "gym_lqr_lanes_rollout")
         return x, u, summary
+
+    # ------------------------------------------------------------- per-lane MPC tracking
+    def mpc_lanes_gains(self, x_opt, u_opt, Q, R, QT, L: int, gains: bool = True, ws=None):
+        """gym_mpc_lanes_gains: the first gain of every MPC window (L = T_pred stages) of every lane along x_opt
+        (B,N,4), u_opt (B,N-1,2).  QT (4,4) is a device tensor (mpc_gains' Q_T; a host array is copied once), never
+        read back.  Returns (ws, K): the filled lqr_lanes_workspace lqr_lanes_rollout takes, and K0 (B,N-1,2,4) on the
+        device (None unless ``gains``)."""
+        x_opt = self.t(x_opt); u_opt = self.t(u_opt)
+        if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
+            raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
+        B, N = x_opt.shape[0], x_opt.shape[1]
+        if tuple(u_opt.shape) != (B, N - 1, 2):
+            raise ValueError(f"u_opt must be ({B},{N - 1},2) for x_opt {tuple(x_opt.shape)}, got {tuple(u_opt.shape)}")
+        L = int(L)
+        if L < 2 or L + 2 > _lib.MPC_MAX_STAGES:
+            raise ValueError(f"T_pred must be in [2, {_lib.MPC_MAX_STAGES - 2}] for per-lane MPC tracking, got {L}")
+        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
+            raise ValueError(f"per-lane MPC tracking needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
+        if not np.array_equal(Qh, Qh.T):
+            raise ValueError(f"Q must be symmetric, got {Qh.tolist()}")
+        QTd = self.t(QT)
+        if tuple(QTd.shape) != (4, 4):
+            raise ValueError(f"QT must be (4,4), got {tuple(QTd.shape)}")
+        if ws is None:
+            ws = self.lqr_lanes_workspace(B, N)
+        ws_bytes = ws.numel() * ws.element_size()
+        need = C.c_int64()
+        _lib.check(self.lib.gym_lqr_lanes_workspace(B, N, C.byref(need)), "gym_lqr_lanes_workspace")
+        if ws_bytes < need.value:
+            raise ValueError(f"the workspace holds {ws_bytes} bytes, {B} lanes of {N} knots need {need.value}")
+        K = torch.empty((B, N - 1, 2, 4), dtype=F64, device=self.device) if gains else None
+        _lib.check(self.lib.gym_mpc_lanes_gains(C.byref(self.model), x_opt.data_ptr(), u_opt.data_ptr(), B, N, L,
+                                                Qh.ctypes.data, Rh.ctypes.data, QTd.data_ptr(), ws.data_ptr(),
+                                                ws_bytes, _lib.ptr(K), self.stream), "gym_mpc_lanes_gains")
+        return ws, K

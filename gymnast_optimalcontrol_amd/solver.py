@@ -82,28 +82,38 @@ class SolveResult:
             raise ValueError(f"t must hold the {N} knot times, got {a['t'].shape}")
         np.savez(path, **a)
 
+    def _track_starts(self, x0, dx0):
+        """The perturbed starts of track_lqr / track_mpc: x0 itself, or x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4)
+        (default: no perturbation)."""
+        if x0 is not None and dx0 is not None:
+            raise ValueError("give x0 or dx0, not both")
+        if x0 is not None:
+            return x0
+        start = self.x[:, 0]
+        if dx0 is None:
+            return start
+        d = torch.as_tensor(np.asarray(dx0.detach().cpu() if isinstance(dx0, torch.Tensor) else dx0, dtype=np.float64),
+                            device=start.device)
+        B = start.shape[0]
+        if tuple(d.shape) == (4,) or tuple(d.shape) == (B, 4):
+            return start + d
+        if d.ndim == 3 and d.shape[0] == B and d.shape[2] == 4:
+            return start[:, None, :] + d
+        raise ValueError(f"dx0 must be (4,), ({B},4) or ({B},P,4), got {tuple(d.shape)}")
+
     def track_lqr(self, x0=None, dx0=None, **kw):
         """LQR tracking of every lane's own result (trajectory_tracking.LQR_tracking_lanes on this result's x, u):
         x0 (B,4) or (B,P,4) perturbed starts, default x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4) (default: no
         perturbation).  Keyword arguments go to LQR_tracking_lanes.  Returns its LqrLanesResult."""
         from . import trajectory_tracking as tt
-        if x0 is not None and dx0 is not None:
-            raise ValueError("give x0 or dx0, not both")
-        if x0 is None:
-            start = self.x[:, 0]
-            if dx0 is None:
-                x0 = start
-            else:
-                d = torch.as_tensor(np.asarray(dx0.detach().cpu() if isinstance(dx0, torch.Tensor) else dx0,
-                                               dtype=np.float64), device=start.device)
-                B = start.shape[0]
-                if tuple(d.shape) == (4,) or tuple(d.shape) == (B, 4):
-                    x0 = start + d
-                elif d.ndim == 3 and d.shape[0] == B and d.shape[2] == 4:
-                    x0 = start[:, None, :] + d
-                else:
-                    raise ValueError(f"dx0 must be (4,), ({B},4) or ({B},P,4), got {tuple(d.shape)}")
-        return tt.LQR_tracking_lanes(self.x, self.u, x0, **kw)
+        return tt.LQR_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
+
+    def track_mpc(self, x0=None, dx0=None, **kw):
+        """Receding-horizon MPC tracking of every lane's own result (trajectory_tracking.MPC_tracking_lanes on this
+        result's x, u); x0 / dx0 as track_lqr.  Keyword arguments (T_pred, Q, R, trajectories, gains) go to
+        MPC_tracking_lanes.  Returns its MpcLanesResult."""
+        from . import trajectory_tracking as tt
+        return tt.MPC_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
 
 
 CHECKPOINT_KEYS = ("x", "u", "cost", "status", "n_iter", "gamma", "n_rollouts", "K", "sigma")

@@ -21,7 +21,9 @@ Batched additions: ``LQR_tracking_batch``, ``solve_mpc_tracking_batch`` and ``so
 take x0 (B,4) and return device tensors; they follow one reference shared by every lane.  ``LQR_tracking_lanes`` /
 ``lqr_gains_lanes`` track every lane's own trajectory (x_opt (B,N,4), u_opt (B,N-1,2), e.g. a batched solve's result):
 per-lane gains and closed-loop rollouts in the kernels of csrc/lqr_lanes.hpp (gym_lqr_lanes_gains /
-gym_lqr_lanes_rollout).  There is no CPU fallback.
+gym_lqr_lanes_rollout).  ``MPC_tracking_lanes`` / ``mpc_gains_lanes`` do the same with the receding-horizon
+MPC (no torque limit): the first gain of every T_pred-stage window along every lane's own trajectory in the kernel of
+csrc/mpc_lanes.hpp (gym_mpc_lanes_gains), then the same closed-loop rollout.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import _lib
 from . import dynamics as _dyn
 from .dynamics import dt, ns, ni  # noqa: F401  (the reference module's namespace, trajectory_tracking.py:3)
 
@@ -43,7 +46,7 @@ X_F = np.array([np.pi, 0.0, 0.0, 0.0])              # :31
 U_F = np.array([0.0, 0.0])                          # :32
 T_PRED = 75                                         # :10
 TAU_MAX = 18.0                                      # :91 (solver_mpc's torque limit, test_constraints)
-MPC_FUSED_MAX_STAGES = 256                          # gym_mpc_gains: T_pred + 2 stages per workgroup's LDS table
+MPC_FUSED_MAX_STAGES = _lib.MPC_MAX_STAGES          # gym_mpc_gains: T_pred + 2 stages per workgroup's LDS table
 
 
 def _eng():
@@ -150,6 +153,24 @@ def _lane_trajectories(eng, x_opt, u_opt):
     return x_opt, u_opt
 
 
+def _lane_starts(eng, x0, x_opt):
+    """x0 (B,4) or (B,P,4) on the device as (B,P,4), and whether it came without the P axis."""
+    B = x_opt.shape[0]
+    x0 = eng.t(x0)
+    if x0.ndim not in (2, 3) or x0.shape[-1] != 4 or x0.shape[0] != B or (x0.ndim == 3 and x0.shape[1] < 1):
+        raise ValueError(f"x0 must be ({B},4) or ({B},P,4) for x_opt {tuple(x_opt.shape)}, got {tuple(x0.shape)}")
+    return x0.reshape(B, -1, 4), x0.ndim == 2
+
+
+def _lane_rollout(eng, ws, x0, N, trajectories, flat):
+    """The closed loop of x0 (B,P,4) on a workspace a per-lane gains call filled (gym_lqr_lanes_rollout); ``flat``
+    drops the P axis again."""
+    x, u, s = eng.lqr_lanes_rollout(ws, x0, N, trajectories=trajectories)
+    if flat:
+        x, u, s = (None if x is None else x[:, 0]), (None if u is None else u[:, 0]), s[:, :, 0]
+    return x, u, s
+
+
 def lqr_gains_lanes(x_opt, u_opt, Q=Q_REG, R=R_REG, QT=QT_REG) -> torch.Tensor:
     """solve_LQR_tracking (:170-203) per lane: x_opt (B,N,4), u_opt (B,N-1,2) -> K (B,N-1,2,4) on the device
     (row 0 of every gain is exactly zero: tau1 is unactuated)."""
@@ -166,15 +187,9 @@ def LQR_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bo
     no use for B P trajectories), ``gains=False`` skips the lane-major copy of K."""
     eng = _eng()
     x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
-    B, N = x_opt.shape[0], x_opt.shape[1]
-    x0 = eng.t(x0)
-    flat = x0.ndim == 2
-    if x0.ndim not in (2, 3) or x0.shape[-1] != 4 or x0.shape[0] != B or (x0.ndim == 3 and x0.shape[1] < 1):
-        raise ValueError(f"x0 must be ({B},4) or ({B},P,4) for x_opt {tuple(x_opt.shape)}, got {tuple(x0.shape)}")
+    x0, flat = _lane_starts(eng, x0, x_opt)
     ws, K = eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=gains)
-    x, u, s = eng.lqr_lanes_rollout(ws, x0.reshape(B, -1, 4), N, trajectories=trajectories)
-    if flat:
-        x, u, s = (None if x is None else x[:, 0]), (None if u is None else u[:, 0]), s[:, :, 0]
+    x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat)
     return LqrLanesResult(x, u, K, s[0], s[1], s[2])
 
 
@@ -197,6 +212,50 @@ def mpc_gains(x_ref, u_ref, T_pred: int = T_PRED, Q=Q_MPC, R=R_MPC, n_steps: int
     K0 = eng.tv_lqr_gains(A_c, B_c, Q, R, QT, L=int(T_pred), nwin=n_steps, all_gains=False,
                           A_pad=Af_c[0], B_pad=Bf_c[0], discretize=True)
     return K0, QT
+
+
+def _mpc_terminal_weight(eng, Q, R) -> torch.Tensor:
+    """Q_T = compute_P_inf on the pad (x_f, u_f) (:31-38) as a device tensor, made by gym_mpc_gains itself once per
+    engine (its model and dt enter the pad's linearisation) and (Q, R): Q_T depends on neither the reference nor
+    T_pred, so this is bit for bit the QT that ``mpc_gains`` returns on the same engine for the same Q, R, and no
+    per-lane call computes or reads it back.  The cached tensor stays private: callers are handed a copy."""
+    key = (np.asarray(Q, dtype=np.float64).tobytes(), np.asarray(R, dtype=np.float64).tobytes())
+    if key not in eng.mpc_qt_cache:
+        x_f, u_f = _final_state(eng)
+        eng.mpc_qt_cache[key] = eng.mpc_gains(torch.cat([x_f, x_f]), u_f, x_f, u_f, Q, R, L=2, nwin=1)[1]
+    return eng.mpc_qt_cache[key]
+
+
+def mpc_gains_lanes(x_opt, u_opt, T_pred: int = T_PRED, Q=Q_MPC, R=R_MPC):
+    """``mpc_gains`` per lane: x_opt (B,N,4), u_opt (B,N-1,2) -> (K0 (B,N-1,2,4), QT (4,4)) on the device.  K0[b, t]
+    is the exact solution of solve_mpc_tracking's QP (:8-69, no torque limit) at control step t of lane b's own
+    trajectory (row 0 of every gain is exactly zero: tau1 is unactuated); QT is ``mpc_gains``' bit for bit."""
+    eng = _eng()
+    x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
+    QT = _mpc_terminal_weight(eng, Q, R)
+    return eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=True)[1], QT.clone()
+
+
+@dataclass
+class MpcLanesResult(LqrLanesResult):
+    """MPC_tracking_lanes' result: LqrLanesResult's fields (K = the windows' first gains K0 (B,N-1,2,4)) and QT (4,4),
+    the terminal weight compute_P_inf gives on the pad (a device tensor, the caller's own copy)."""
+    QT: torch.Tensor
+
+
+def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bool = True, T_pred: int = T_PRED,
+                       Q=Q_MPC, R=R_MPC) -> MpcLanesResult:
+    """Receding-horizon MPC tracking of every lane's OWN trajectory (main.py task_2's result into task_4, per lane;
+    solve_mpc_tracking :8-69 without a torque limit): lane b's first gains come from the T_pred-stage windows along
+    (x_opt[b], u_opt[b]) and its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are simulated in
+    closed loop against them.  Shapes, ``trajectories`` and ``gains`` as LQR_tracking_lanes."""
+    eng = _eng()
+    x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
+    x0, flat = _lane_starts(eng, x0, x_opt)
+    QT = _mpc_terminal_weight(eng, Q, R)
+    ws, K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=gains)
+    x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat)
+    return MpcLanesResult(x, u, K, s[0], s[1], s[2], QT.clone())
 
 
 def solve_mpc_tracking_batch(x0, x_ref, u_ref, T_pred: int = T_PRED):

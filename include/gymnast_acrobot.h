@@ -448,6 +448,23 @@ int gym_lqr_lanes_gains(const gym_model* m, const double* x_opt, const double* u
 int gym_lqr_lanes_rollout(const gym_model* m, const double* x0, int64_t B, int32_t P, int32_t N, const void* ws,
                           int64_t ws_bytes, double* x_out, double* u_out, double* summary_out, void* stream);
 
+/* ---------------- Per-lane MPC tracking: receding-horizon gains along each lane's own trajectory ----------------
+ * (main.py task_2's result fed to task_4, per lane.)  solve_mpc_tracking (trajectory_tracking.py:8-69) without a
+ * torque limit, per lane: the QP of control step t is solved exactly by the first gain K0_t of window t's recursion
+ * over stages t .. t+L-2 of the lane's own linearisation (L = T_pred), the pad at x_f = (pi,0,0,0), u_f = 0 past
+ * stage N-1, from P = Q_T.  The call fills a gym_lqr_lanes_workspace buffer (packed x_opt, u_opt, and row 1 of K0_t
+ * as the K1 stream; padding lanes zero), so gym_lqr_lanes_rollout runs the closed loop u_t = u_opt_t + K0_t (x_t -
+ * x_opt_t) on it as is; no workspace function of its own.  x_opt (B,N,4), u_opt (B,N-1,2) [device, lane-major];
+ * Q, R [host]; QT_dev [device, 16 doubles]: Q_T = compute_P_inf on the pad as gym_mpc_gains' QT_out holds it (never
+ * read back: no host synchronisation; its upper triangle is used).  K_out optional: (B,N-1,2,4), row 0 = 0.  A
+ * lane's results depend on that lane's inputs only.
+ * GYM_EINVAL: a required pointer NULL, B < 1, N < 2, L < 2, L + 2 > 256, Bp > GYM_MAX_BP, ws_bytes too small,
+ * R not diagonal or R[1][1] <= 0, Q not symmetric.
+ * Additive to ABI 18: no existing entry point or structure changed. */
+int gym_mpc_lanes_gains(const gym_model* m, const double* x_opt, const double* u_opt, int64_t B, int32_t N, int32_t L,
+                        const double Q[16], const double R[4], const double* QT_dev, void* ws, int64_t ws_bytes,
+                        double* K_out, void* stream);
+
 /* [host] create / destroy the events of a gym_timing; collect = add the elapsed time of every pending
  * pair (call only after the stream that recorded them has been synchronised). */
 int gym_timing_create(gym_timing* t);
