@@ -11,7 +11,8 @@
 // feed-forward / feedback sequence (simulate_tracking :206-216 and the MPC loop :43-60), one lane per thread
 // with the gains, reference and feed-forward read through wave-uniform (scalar) loads.
 // Per-lane LQR tracking (every lane follows its OWN trajectory, so the gains are per-lane streams) is lqr_lanes.hpp;
-// per-lane MPC tracking (every window of every lane has its own first gain) is mpc_lanes.hpp.
+// per-lane MPC tracking (every window of every lane has its own first gain) is mpc_lanes.hpp; with the torque limit
+// (every lane's own QPs) it is mpc_box_lanes.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -988,6 +989,7 @@ inline bool box_weights_ok(const double* R) {   // the channel split needs a dia
 
 #include "lqr_lanes.hpp"   // per-lane LQR tracking: every lane follows its own trajectory
 #include "mpc_lanes.hpp"   // per-lane MPC tracking: the first gain of every window of every lane
+#include "mpc_box_lanes.hpp"   // per-lane torque-limited MPC tracking: each lane's QPs along its own trajectory
 
 inline M44 m44(const double* p) { M44 m; for (int i = 0; i < 16; ++i) m.v[i] = p[i]; return m; }
 inline M22 m22(const double* p) { M22 m; for (int i = 0; i < 4; ++i) m.v[i] = p[i]; return m; }
@@ -1220,6 +1222,41 @@ int gym_mpc_lanes_gains(const gym_model* m, const double* x_opt, const double* u
     if (K_out)
         hipLaunchKernelGGL(k_lqr_unpack_gains, dim3((unsigned)(groups * ntk)), dim3(LL_THREADS), 0, st, ks,
                            reinterpret_cast<double2*>(K_out), B, lo.Bp, T, ntk);
+    return launch_status();
+}
+
+
+// ---- per-lane torque-limited MPC tracking (mpc_box_lanes.hpp) ----
+static bool box_lanes_sizes_ok(int64_t B, int32_t P, int32_t N, int32_t L) {
+    return B >= 1 && P >= 1 && N >= 2 && L >= 2 && L + 2 <= kMpcMaxStages && B <= GYM_MAX_BP / P;
+}
+
+int gym_mpc_box_lanes_workspace(int64_t B, int32_t P, int32_t L, int64_t* bytes_out) {
+    if (!bytes_out || !box_lanes_sizes_ok(B, P, 2, L)) return GYM_EINVAL;
+    *bytes_out = box_lanes_layout(B, P, L).bytes;
+    return 0;
+}
+
+// solve_mpc_tracking's closed loop (trajectory_tracking.py:43-67) with solver_mpc's test_constraints (:87-114) per lane
+int gym_mpc_box_lanes_rollout(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0, int64_t B,
+                              int32_t P, int32_t N, int32_t L, const double Q[16], const double R[4],
+                              const double* QT_dev, double tau_max, int32_t max_qp_iters, void* ws, int64_t ws_bytes,
+                              double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
+                              int32_t* unconverged_out, void* s) {
+    if (!m || !x_opt || !u_opt || !x0 || !Q || !R || !QT_dev || !ws || !summary_out || !unconverged_out ||
+        !box_lanes_sizes_ok(B, P, N, L) || !(tau_max > 0.0 && tau_max <= 1.7976931348623157e308) || max_qp_iters < 1 ||
+        !box_weights_ok(R) || !lanes_sym(Q) || (x_out == nullptr) != (u_out == nullptr))
+        return GYM_EINVAL;
+    const BoxLanesLayout lo = box_lanes_layout(B, P, L);
+    if (ws_bytes < lo.bytes) return GYM_EINVAL;
+    char* base = static_cast<char*>(ws);
+    const int nblk = (P + 63) / 64;                        // B nblk <= B P <= GYM_MAX_BP: far below the grid limit
+    const size_t lds = sizeof(double) * (kBoxRow + 4) * (L - 1);
+    hipLaunchKernelGGL(k_mpc_box_lane_rollout, dim3((unsigned)(B * nblk)), dim3(64), lds, (hipStream_t)s, Dyn(*m),
+                       m44(Q), R[3], QT_dev, tau_max, max_qp_iters, reinterpret_cast<const double2*>(x_opt),
+                       reinterpret_cast<const double2*>(u_opt), x0, (int)P, (int)N, (int)L, nblk,
+                       reinterpret_cast<double*>(base), reinterpret_cast<int32_t*>(base + lo.off_st), x_out, u_out,
+                       summary_out, qp_iters_out, unconverged_out);
     return launch_status();
 }
 

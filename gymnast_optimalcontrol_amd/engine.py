@@ -585,3 +585,69 @@ class AcrobotEngine:
                                                 Qh.ctypes.data, Rh.ctypes.data, QTd.data_ptr(), ws.data_ptr(),
                                                 ws_bytes, _lib.ptr(K), self.stream), "gym_mpc_lanes_gains")
         return ws, K
+
+    # ------------------------------------------------------------- per-lane torque-limited MPC tracking
+    BOX_LANES_WS_SHARE = 0.5    # mpc_box_lanes_rollout's own workspace: at most this share of the free device memory
+
+    def mpc_box_lanes_workspace(self, B: int, P: int, L: int) -> int:
+        """Bytes of gym_mpc_box_lanes_rollout's caller-owned workspace for B lanes x P starts, windows of L stages."""
+        need = C.c_int64()
+        _lib.check(self.lib.gym_mpc_box_lanes_workspace(int(B), int(P), int(L), C.byref(need)),
+                   "gym_mpc_box_lanes_workspace")
+        return need.value
+
+    def mpc_box_lanes_rollout(self, x_opt, u_opt, x0, Q, R, QT, L: int, tau_max: float, max_qp_iters: int = 32,
+                              trajectories: bool = True, max_ws_bytes: int | None = None):
+        """gym_mpc_box_lanes_rollout: the torque-limited MPC closed loop of every lane along its own x_opt (B,N,4),
+        u_opt (B,N-1,2) from the starts x0 (B,P,4); QT (4,4) a device tensor as in mpc_lanes_gains.  Returns device
+        tensors (x (B,P,N,4), u (B,P,N-1,2), summary (3,B,P), qp_iters (B,P,N-1) int32, unconverged (B,P) int32); x, u
+        and qp_iters are None unless ``trajectories``.  The sweep workspace (about 80 (L-1) bytes per lane and start) is
+        allocated here; a batch whose workspace would exceed ``max_ws_bytes`` (default: BOX_LANES_WS_SHARE of the free
+        device memory) runs in chunks of whole lanes, one call each -- the same results, lanes being independent."""
+        x_opt = self.t(x_opt); u_opt = self.t(u_opt); x0 = self.t(x0)
+        if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
+            raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
+        B, N = x_opt.shape[0], x_opt.shape[1]
+        if tuple(u_opt.shape) != (B, N - 1, 2):
+            raise ValueError(f"u_opt must be ({B},{N - 1},2) for x_opt {tuple(x_opt.shape)}, got {tuple(u_opt.shape)}")
+        if x0.ndim != 3 or x0.shape[0] != B or x0.shape[1] < 1 or x0.shape[2] != 4:
+            raise ValueError(f"x0 must be ({B},P,4), got {tuple(x0.shape)}")
+        P, L = x0.shape[1], int(L)
+        if L < 2 or L + 2 > _lib.MPC_MAX_STAGES:
+            raise ValueError(f"T_pred must be in [2, {_lib.MPC_MAX_STAGES - 2}] for the torque-limited QP, got {L}")
+        if B * P > _lib.MAX_BP:
+            raise ValueError(f"{B} lanes x {P} starts exceed {_lib.MAX_BP} closed loops per call")
+        if not (np.isfinite(tau_max) and tau_max > 0):
+            raise ValueError(f"tau_max must be finite and positive, got {tau_max}")
+        if int(max_qp_iters) < 1:
+            raise ValueError(f"max_qp_iters must be at least 1, got {max_qp_iters}")
+        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
+            raise ValueError(f"the torque-limited QP needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
+        if not np.array_equal(Qh, Qh.T):
+            raise ValueError(f"Q must be symmetric, got {Qh.tolist()}")
+        QTd = self.t(QT)
+        if tuple(QTd.shape) != (4, 4):
+            raise ValueError(f"QT must be (4,4), got {tuple(QTd.shape)}")
+        per_lane = self.mpc_box_lanes_workspace(1, P, L)
+        if max_ws_bytes is None:
+            max_ws_bytes = int(self.BOX_LANES_WS_SHARE * torch.cuda.mem_get_info(self.device)[0])
+        chunk = max(1, min(B, int(max_ws_bytes) // per_lane))
+        ws = torch.empty(chunk * per_lane, dtype=torch.uint8, device=self.device)
+        x = torch.empty((B, P, N, 4), dtype=F64, device=self.device) if trajectories else None
+        u = torch.empty((B, P, N - 1, 2), dtype=F64, device=self.device) if trajectories else None
+        it = torch.empty((B, P, N - 1), dtype=torch.int32, device=self.device) if trajectories else None
+        summary = torch.empty((3, B, P), dtype=F64, device=self.device)
+        unconv = torch.empty((B, P), dtype=torch.int32, device=self.device)
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            sm = summary if chunk >= B else torch.empty((3, b1 - b0, P), dtype=F64, device=self.device)
+            _lib.check(self.lib.gym_mpc_box_lanes_rollout(
+                C.byref(self.model), x_opt[b0:b1].data_ptr(), u_opt[b0:b1].data_ptr(), x0[b0:b1].data_ptr(), b1 - b0,
+                P, N, L, Qh.ctypes.data, Rh.ctypes.data, QTd.data_ptr(), float(tau_max), int(max_qp_iters),
+                ws.data_ptr(), ws.numel(), _lib.ptr(None if x is None else x[b0:b1]),
+                _lib.ptr(None if u is None else u[b0:b1]), sm.data_ptr(), _lib.ptr(None if it is None else it[b0:b1]),
+                unconv[b0:b1].data_ptr(), self.stream), "gym_mpc_box_lanes_rollout")
+            if sm is not summary:
+                summary[:, b0:b1] = sm
+        return x, u, summary, it, unconv

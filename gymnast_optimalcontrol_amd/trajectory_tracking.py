@@ -23,7 +23,9 @@ take x0 (B,4) and return device tensors; they follow one reference shared by eve
 per-lane gains and closed-loop rollouts in the kernels of csrc/lqr_lanes.hpp (gym_lqr_lanes_gains /
 gym_lqr_lanes_rollout).  ``MPC_tracking_lanes`` / ``mpc_gains_lanes`` do the same with the receding-horizon
 MPC (no torque limit): the first gain of every T_pred-stage window along every lane's own trajectory in the kernel of
-csrc/mpc_lanes.hpp (gym_mpc_lanes_gains), then the same closed-loop rollout.  There is no CPU fallback.
+csrc/mpc_lanes.hpp (gym_mpc_lanes_gains), then the same closed-loop rollout; with ``tau_max`` every
+closed loop solves its own torque-limited QPs along its own lane's trajectory in the kernel of csrc/mpc_box_lanes.hpp
+(gym_mpc_box_lanes_rollout).  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -243,19 +245,51 @@ class MpcLanesResult(LqrLanesResult):
     QT: torch.Tensor
 
 
+@dataclass
+class MpcBoxLanesResult(MpcLanesResult):
+    """MPC_tracking_lanes' result with a torque limit: MpcLanesResult's fields (K = the windows' unconstrained first
+    gains, the first iterate of every QP), unconverged (B,P) int32 = the QPs of that closed loop that reached
+    ``max_qp_iters`` without settling (their clipped last iterate was applied), and qp_iters (B,P,N-1) int32
+    active-set sweeps per QP (None with ``trajectories=False``).  An x0 of shape (B,4) drops the P axis of both."""
+    unconverged: torch.Tensor
+    qp_iters: torch.Tensor | None
+
+
 def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bool = True, T_pred: int = T_PRED,
-                       Q=Q_MPC, R=R_MPC) -> MpcLanesResult:
+                       Q=Q_MPC, R=R_MPC, **limit) -> MpcLanesResult:
     """Receding-horizon MPC tracking of every lane's OWN trajectory (main.py task_2's result into task_4, per lane;
-    solve_mpc_tracking :8-69 without a torque limit): lane b's first gains come from the T_pred-stage windows along
-    (x_opt[b], u_opt[b]) and its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are simulated in
-    closed loop against them.  Shapes, ``trajectories`` and ``gains`` as LQR_tracking_lanes."""
+    solve_mpc_tracking :8-69): lane b's first gains come from the T_pred-stage windows along (x_opt[b], u_opt[b]) and
+    its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are simulated in closed loop against them.
+    Shapes, ``trajectories`` and ``gains`` as LQR_tracking_lanes.
+
+    Two more keywords, ``tau_max=None`` and ``max_qp_iters=32``, are taken through ``**limit`` (the named keywords
+    above are a pinned part of the interface; any other name raises TypeError as an unknown keyword does).
+    ``tau_max`` (None: the reference's default, no limit) is solver_mpc's torque limit (test_constraints, :87-114;
+    the reference uses 18): every stage of every window obeys |u_opt[b][t] + u_t| <= tau_max, so every control step
+    of every closed loop owns an inequality-constrained QP, solved by the active set of the shared-reference path
+    (at most ``max_qp_iters`` sweeps each) in the kernel of csrc/mpc_box_lanes.hpp (gym_mpc_box_lanes_rollout; DESIGN
+    4.7).  Returns an MpcBoxLanesResult then; where no bound is ever active its x, u and summaries are the
+    unlimited call's bit for bit."""
+    tau_max, max_qp_iters = limit.pop("tau_max", None), limit.pop("max_qp_iters", 32)
+    if limit:
+        raise TypeError(f"MPC_tracking_lanes() got an unexpected keyword argument {sorted(limit)[0]!r}")
+    if tau_max is not None:
+        _check_box(tau_max, T_pred, max_qp_iters)
     eng = _eng()
     x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
     x0, flat = _lane_starts(eng, x0, x_opt)
     QT = _mpc_terminal_weight(eng, Q, R)
-    ws, K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=gains)
-    x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat)
-    return MpcLanesResult(x, u, K, s[0], s[1], s[2], QT.clone())
+    if tau_max is None:
+        ws, K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=gains)
+        x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat)
+        return MpcLanesResult(x, u, K, s[0], s[1], s[2], QT.clone())
+    K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=True)[1] if gains else None
+    x, u, s, it, unconv = eng.mpc_box_lanes_rollout(x_opt, u_opt, x0, Q, R, QT, int(T_pred), float(tau_max),
+                                                    int(max_qp_iters), trajectories=trajectories)
+    if flat:
+        x, u, it = (None if x is None else x[:, 0]), (None if u is None else u[:, 0]), (None if it is None else it[:, 0])
+        s, unconv = s[:, :, 0], unconv[:, 0]
+    return MpcBoxLanesResult(x, u, K, s[0], s[1], s[2], QT.clone(), unconv, it)
 
 
 def solve_mpc_tracking_batch(x0, x_ref, u_ref, T_pred: int = T_PRED):

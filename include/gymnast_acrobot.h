@@ -465,6 +465,32 @@ int gym_mpc_lanes_gains(const gym_model* m, const double* x_opt, const double* u
                         const double Q[16], const double R[4], const double* QT_dev, void* ws, int64_t ws_bytes,
                         double* K_out, void* stream);
 
+/* ---------------- Per-lane torque-limited MPC tracking: each lane's own QPs along its own trajectory ----------------
+ * (main.py task_2's result fed to task_4 with the actuator limit, per lane.)  solve_mpc_tracking's closed loop
+ * (trajectory_tracking.py:43-67) with solver_mpc's test_constraints on (:87-114), per lane b and perturbed start p:
+ * per control step s, e = x - x_opt[b][s], the QP of window s (stages s .. s+L-2 of the lane's own linearisation,
+ * the pad at x_f = (pi,0,0,0), u_f = 0 past stage N-2, -tau_max <= u_opt[b][t] + u_t <= tau_max on every stage;
+ * gym_mpc_box_rollout's active set, first iterate = the window's unconstrained gains, made on the spot),
+ * u_real[s] = u_opt[b][s] + u_0 (a first control on its bound applies the limit itself), one RK4 step.  With no bound
+ * active anywhere the results are gym_mpc_lanes_gains + gym_lqr_lanes_rollout's bit for bit.  x_opt (B,N,4), u_opt
+ * (B,N-1,2), x0 (B,P,4) [device, lane-major]; Q, R [host]; QT_dev [device, 16 doubles]: Q_T as gym_mpc_gains' QT_out
+ * holds it (never read back).  Outputs [device], lane-major: x_out (B,P,N,4), u_out (B,P,N-1,2) optional (both or
+ * neither); summary_out (3,B,P) as gym_lqr_lanes_rollout defines it; qp_iters_out (B,P,N-1) optional: active-set
+ * sweeps per QP; unconverged_out (B,P): QPs that reached max_qp_iters (clipped last iterate applied).  A lane's
+ * results depend on that lane's inputs and that start only (not on B, P or its position).
+ * GYM_EINVAL: a required pointer NULL, B < 1, P < 1, N < 2, L < 2, L + 2 > 256, B P > GYM_MAX_BP, tau_max not finite
+ * and positive, max_qp_iters < 1, R not diagonal or R[1][1] <= 0, Q not symmetric, exactly one of x_out / u_out,
+ * ws_bytes too small.
+ * Additive to ABI 18: no existing entry point or structure changed. */
+/* [host] bytes of the workspace of B lanes x P starts, windows of L stages: per (lane, start), (k, d, x, u) of every
+ * stage and the stage states, per lane in (slot, stage, start) layout */
+int gym_mpc_box_lanes_workspace(int64_t B, int32_t P, int32_t L, int64_t* bytes_out);
+int gym_mpc_box_lanes_rollout(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0, int64_t B,
+                              int32_t P, int32_t N, int32_t L, const double Q[16], const double R[4],
+                              const double* QT_dev, double tau_max, int32_t max_qp_iters, void* ws, int64_t ws_bytes,
+                              double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
+                              int32_t* unconverged_out, void* stream);
+
 /* [host] create / destroy the events of a gym_timing; collect = add the elapsed time of every pending
  * pair (call only after the stream that recorded them has been synchronised). */
 int gym_timing_create(gym_timing* t);
