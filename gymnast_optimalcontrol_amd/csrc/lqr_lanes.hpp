@@ -1,6 +1,7 @@
 // Per-lane LQR tracking: every lane tracks its OWN trajectory (x_opt, u_opt), e.g. the swing-up the batched Newton
 // solver produced for it (main.py: task_2's result fed to task_3, per lane).  Part of the tracking_kernels.hip
-// translation unit (included inside its anonymous namespace).
+// translation unit (included inside its anonymous namespace; gym:: and Dyn come from acrobot_device.hpp, which the .hip
+// includes ahead of the namespace).
 //
 //   gains    solve_LQR_tracking (trajectory_tracking.py:170-203) per lane: linearise along the lane's trajectory,
 //            backward recursion K = -inv(R + B'PB) B'PA, P <- Q + A'PA + (A'PB) K from P = QT;
@@ -17,7 +18,8 @@
 // so a wavefront's access to one stage is contiguous (2 KiB for pairs, 512 B per plane).
 #pragma once
 
-#include "newton_streams.hpp"
+#include "mpc_gains.hpp"        // wave_lds_order
+#include "newton_streams.hpp"   // BLK, wix / pix, ld_nt / st_nt
 
 constexpr int LL_THREADS = 256;   // the LDS-tiled transposes: 4 wavefronts per workgroup
 constexpr int LL_PITCH = 65;      // LDS row pitch in doubles (64 lanes + 1: conflict-free transposed reads)
@@ -109,6 +111,9 @@ __global__ __launch_bounds__(LL_THREADS) void k_lqr_unpack_gains(const double2* 
 
 // Symmetric 4x4 in 10 registers: the upper triangle, row by row
 struct Sym4 { double v[10]; };   // (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
+__host__ __device__ inline Sym4 sym4(const double* M) {   // of a symmetric row-major 4x4
+    return Sym4{{M[0], M[1], M[2], M[3], M[5], M[6], M[7], M[10], M[11], M[15]}};
+}
 
 // One step of the reference's recursion (trajectory_tracking.py:195-200) on the acrobot's discretised stage
 //   A_d = I + dt A_c: rows 0, 1 = [1 0 h 0], [0 1 0 h], rows 2, 3 = a2, a3;   B_d = [0, b], b = (0, 0, b2, b3)'
@@ -307,7 +312,4 @@ inline bool lanes_sym(const double* M) {
         for (int j = i + 1; j < 4; ++j)
             if (!(M[4 * i + j] == M[4 * j + i])) return false;
     return true;
-}
-inline Sym4 sym4(const double* M) {
-    return Sym4{{M[0], M[1], M[2], M[3], M[5], M[6], M[7], M[10], M[11], M[15]}};
 }

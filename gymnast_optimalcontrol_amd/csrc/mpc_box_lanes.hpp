@@ -1,9 +1,9 @@
 // Torque-limited per-lane MPC tracking: every lane tracks its OWN trajectory with the receding-horizon MPC of
 // trajectory_tracking.py:43-67 under solver_mpc's test_constraints (:87-114), |u_opt_t + u_t| <= tau_max on every
 // stage of every window (main.py: task_2's result fed to task_4 with the actuator limit, per lane).  Part of the
-// tracking_kernels.hip translation unit (included inside its anonymous namespace, after mpc_lanes.hpp).
+// tracking_kernels.hip translation unit (included inside its anonymous namespace).
 //
-// The QP is tracking_kernels.hip's "Torque-limited MPC" (box_qp_lane and its three passes, unchanged); what differs
+// The QP is mpc_box.hpp's "Torque-limited MPC" (box_qp_lane and its three passes, unchanged); what differs
 // from k_mpc_box_rollout is where the window comes from.  There every lane shares one reference, so a stage table and
 // K_all (every gain of every window) are made once.  Here they are per-lane data, and a per-lane K_all (1.2 MB at
 // N = 501, L = 75) cannot be stored: the wavefront makes both on the spot.
@@ -25,7 +25,8 @@
 // box_qp_lane's wave vote.  A lane's results depend on that lane's inputs and that start only.
 #pragma once
 
-#include "mpc_lanes.hpp"
+#include "mpc_box.hpp"     // M44, BoxWin, BoxWs, box_qp_lane, box_apply, kBoxRow, kBoxSlots, wave_lds_order
+#include "mpc_lanes.hpp"   // ML_ROWS; Sym4, lqr_lane_stage, lqr_lane_step of lqr_lanes.hpp
 
 // workspace of B lanes x P starts, windows of L stages: the doubles of every (lane, start), then the stage states
 struct BoxLanesLayout {
@@ -91,8 +92,7 @@ __global__ __launch_bounds__(64) void k_mpc_box_lane_rollout(Dyn m, M44 Q, doubl
         xl[0] = make_double2(n0, n1);
         xl[1] = make_double2(n2, n3);
     }
-    const Sym4 Qs = Sym4{{Q.v[0], Q.v[1], Q.v[2], Q.v[3], Q.v[5], Q.v[6], Q.v[7], Q.v[10], Q.v[11], Q.v[15]}};
-    const Sym4 QTs = Sym4{{QT[0], QT[1], QT[2], QT[3], QT[5], QT[6], QT[7], QT[10], QT[11], QT[15]}};
+    const Sym4 Qs = sym4(Q.v), QTs = sym4(QT);
     const gym::PolyRegs pk = gym::poly_vgprs();
     int unconv = 0;
     double emax = 0.0, umax = 0.0;

@@ -1,9 +1,9 @@
 // Per-lane MPC tracking: every lane tracks its OWN trajectory with the receding-horizon MPC of
 // trajectory_tracking.py:8-69 (main.py: task_2's result fed to task_4, per lane).  Part of the tracking_kernels.hip
-// translation unit (included inside its anonymous namespace, after lqr_lanes.hpp).
+// translation unit (included inside its anonymous namespace).
 //
 // Without a torque limit the QP of control step t is solved exactly by the first gain of window t's finite-horizon
-// recursion (tracking_kernels.hip, "Fused MPC gains"): stages t .. t+L-2 of the lane's own linearisation, the pad
+// recursion (mpc_gains.hpp, "Fused MPC gains"): stages t .. t+L-2 of the lane's own linearisation, the pad
 // (A_f, B_f) at x_f = (pi, 0, 0, 0), u_f = 0 past stage S = N-1, from P = Q_T = compute_P_inf on the pad.  The pad and
 // Q_T do not depend on the lane; the stages do.  The closed loop u_t = u_opt_t + K0_t (x_t - x_opt_t) is exactly
 // k_lqr_lane_rollout on a K1 stream, so only the gains are new: this file fills lqr_lanes.hpp's workspace.
@@ -18,7 +18,7 @@
 // (lqr_lane_step, P in 10 registers) and keeps the last k.  Row 0 of every gain is exactly zero (lqr_lanes.hpp).
 #pragma once
 
-#include "lqr_lanes.hpp"
+#include "lqr_lanes.hpp"   // Sym4, lqr_lane_stage, lqr_lane_step, wix
 
 constexpr int ML_W = 256;            // windows (threads) per workgroup: 64 and 128 were 4.6 % and 3.4 % slower
 constexpr int ML_ROWS = 10;          // doubles per stage: a2[4], a3[4], b2, b3
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(W) void k_mpc_lane_gains(Dyn m, Sym4 Q, const doubl
     }
     __syncthreads();
     if (t >= T) return;
-    Sym4 P = Sym4{{QT[0], QT[1], QT[2], QT[3], QT[5], QT[6], QT[7], QT[10], QT[11], QT[15]}};
+    Sym4 P = sym4(QT);
     const double* row = ml_tab + w;                         // stage s of this window: row[c nst + s]
     double k[4];
     for (int s = L - 2; s >= 0; --s) {                      // the workgroup's other wavefronts cover the LDS latency:

@@ -1,8 +1,11 @@
 """Batched tensor-level front end of the HIP engine (device tensors in, device tensors out).
 
 Every method is a thin launcher over one C-ABI entry point of include/gymnast_acrobot.h; the
-arithmetic runs in the gfx950 kernels of csrc/acrobot_kernels.hip.  Inputs are fp64 tensors
-(any device / numpy are copied to the engine's HIP device); outputs stay on the device.
+arithmetic runs in the gfx950 kernels of csrc/: the Newton solver and its primitives in acrobot_kernels.hip
+(kernels in newton_*.hpp), the trackers in tracking_kernels.hip (kernels in tracking_dense.hpp, mpc_gains.hpp,
+track_rollout.hpp, mpc_box.hpp and the per-lane lqr_lanes.hpp, mpc_lanes.hpp, mpc_box_lanes.hpp).  Inputs are fp64
+tensors (any device / numpy are copied to the engine's HIP device); outputs stay on the device.  The trackers'
+argument checks are the module-level check_* functions at the end: they need no device and no engine.
 
 Lane-major shapes follow the reference stacked over lanes: x (B,N,4), u (B,T,2), K (B,T,2,4),
 sigma (B,T,2).  Internally trajectories live in the SoA "pairs" layout (see the header).
@@ -335,13 +338,6 @@ class AcrobotEngine:
                 dJ[:B])
 
     # ------------------------------------------------------------------ LQR / MPC trackers
-    @staticmethod
-    def _host_mat(M, n, name):
-        M = np.ascontiguousarray(np.asarray(M, dtype=np.float64))
-        if M.shape != (n, n):
-            raise ValueError(f"{name} must be {n}x{n}, got {M.shape}")
-        return M
-
     def tv_lqr_gains(self, A, Bm, Q, R, QT, L: int, nwin: int = 1, all_gains: bool = True, A_pad=None,
                      B_pad=None, discretize: bool = False) -> torch.Tensor:
         """Windowed time-varying LQR gains (gym_tv_lqr_gains): stages A (S,4,4), B (S,4,2) on the device.
@@ -350,7 +346,7 @@ class AcrobotEngine:
         S = A.shape[0]
         Ap = None if A_pad is None else self.t(A_pad).reshape(4, 4)
         Bp_ = None if B_pad is None else self.t(B_pad).reshape(4, 2)
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
         QTd = self.t(QT).reshape(4, 4)                 # device: e.g. dare_fixed_point's P, no host round trip
         out = torch.empty(((L - 1) if all_gains else nwin, 2, 4), dtype=F64, device=self.device)
         _lib.check(self.lib.gym_tv_lqr_gains(A.data_ptr(), Bm.data_ptr(), S, _lib.ptr(Ap), _lib.ptr(Bp_),
@@ -362,7 +358,7 @@ class AcrobotEngine:
     def dare_fixed_point(self, A, Bm, Q, R, max_iter: int = 1000, tol: float = 1e-6):
         """compute_P_inf on the device: returns (P (4,4), iterations (1,) int32), both device tensors (no sync)."""
         A = self.t(A).reshape(4, 4); Bm = self.t(Bm).reshape(4, 2)
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
         P = torch.empty((4, 4), dtype=F64, device=self.device)
         it = torch.zeros(1, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.gym_dare_fixed_point(A.data_ptr(), Bm.data_ptr(), Qh.ctypes.data, Rh.ctypes.data,
@@ -370,24 +366,29 @@ class AcrobotEngine:
                    "gym_dare_fixed_point")
         return P, it
 
-    def mpc_gains(self, x_ref, u_ref, x_f, u_f, Q, R, L: int, nwin: int, max_iter: int = 1000, tol: float = 1e-6):
-        """Fused MPC gains (gym_mpc_gains): stage linearisations of (x_ref, u_ref) and of the pad (x_f, u_f),
-        Q_T = compute_P_inf(A_f, B_f, Q, R), and each window's first gain.  Returns device tensors
-        (K0 (nwin,2,4), Q_T (4,4), iterations (1,) int32); no host synchronisation."""
+    def _mpc_gains(self, every, x_ref, u_ref, x_f, u_f, Q, R, L, nwin, max_iter, tol):
+        """gym_mpc_gains_all (``every`` gain of every window) or gym_mpc_gains (each window's first gain)."""
         x_ref = self.t(x_ref).reshape(-1, 4); u_ref = self.t(u_ref).reshape(-1, 2)
         x_f = self.t(x_f).reshape(4); u_f = self.t(u_f).reshape(2)
         S = x_ref.shape[0] - 1
         if u_ref.shape[0] < S:
             raise ValueError(f"u_ref must hold {S} stages, got {u_ref.shape[0]}")
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
-        K = torch.empty((nwin, 2, 4), dtype=F64, device=self.device)
+        Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
+        K = torch.empty((nwin, int(L) - 1, 2, 4) if every else (nwin, 2, 4), dtype=F64, device=self.device)
         P = torch.empty((4, 4), dtype=F64, device=self.device)
         it = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.gym_mpc_gains(C.byref(self.model), x_ref.data_ptr(), u_ref.data_ptr(), S, x_f.data_ptr(),
-                                          u_f.data_ptr(), Qh.ctypes.data, Rh.ctypes.data, int(L), int(nwin),
-                                          int(max_iter), float(tol), K.data_ptr(), P.data_ptr(), it.data_ptr(),
-                                          self.stream), "gym_mpc_gains")
+        name = "gym_mpc_gains_all" if every else "gym_mpc_gains"
+        _lib.check(getattr(self.lib, name)(C.byref(self.model), x_ref.data_ptr(), u_ref.data_ptr(), S, x_f.data_ptr(),
+                                           u_f.data_ptr(), Qh.ctypes.data, Rh.ctypes.data, int(L), int(nwin),
+                                           int(max_iter), float(tol), K.data_ptr(), P.data_ptr(), it.data_ptr(),
+                                           self.stream), name)
         return K, P, it
+
+    def mpc_gains(self, x_ref, u_ref, x_f, u_f, Q, R, L: int, nwin: int, max_iter: int = 1000, tol: float = 1e-6):
+        """Fused MPC gains (gym_mpc_gains): stage linearisations of (x_ref, u_ref) and of the pad (x_f, u_f),
+        Q_T = compute_P_inf(A_f, B_f, Q, R), and each window's first gain.  Returns device tensors
+        (K0 (nwin,2,4), Q_T (4,4), iterations (1,) int32); no host synchronisation."""
+        return self._mpc_gains(False, x_ref, u_ref, x_f, u_f, Q, R, L, nwin, max_iter, tol)
 
     def lq_forward(self, A, Bm, K, x0, L: int, A_pad=None, B_pad=None, discretize: bool = False):
         """One window's LQ forward pass: X (L,4), U (L-1,2)."""
@@ -424,26 +425,17 @@ class AcrobotEngine:
                       tol: float = 1e-6):
         """gym_mpc_gains_all: mpc_gains with every stage's gain of every window.  Returns device tensors
         (K_all (nwin,L-1,2,4), Q_T (4,4), iterations (1,) int32); K_all[:, 0] is mpc_gains' K0 bit for bit."""
-        x_ref = self.t(x_ref).reshape(-1, 4); u_ref = self.t(u_ref).reshape(-1, 2)
-        x_f = self.t(x_f).reshape(4); u_f = self.t(u_f).reshape(2)
-        S = x_ref.shape[0] - 1
-        if u_ref.shape[0] < S:
-            raise ValueError(f"u_ref must hold {S} stages, got {u_ref.shape[0]}")
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
-        K = torch.empty((nwin, int(L) - 1, 2, 4), dtype=F64, device=self.device)
-        P = torch.empty((4, 4), dtype=F64, device=self.device)
-        it = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.gym_mpc_gains_all(C.byref(self.model), x_ref.data_ptr(), u_ref.data_ptr(), S,
-                                              x_f.data_ptr(), u_f.data_ptr(), Qh.ctypes.data, Rh.ctypes.data, int(L),
-                                              int(nwin), int(max_iter), float(tol), K.data_ptr(), P.data_ptr(),
-                                              it.data_ptr(), self.stream), "gym_mpc_gains_all")
-        return K, P, it
+        return self._mpc_gains(True, x_ref, u_ref, x_f, u_f, Q, R, L, nwin, max_iter, tol)
+
+    def _ws_bytes(self, name: str, *sizes) -> int:
+        """What the workspace-size entry point ``name`` answers for ``sizes``."""
+        need = C.c_int64()
+        _lib.check(getattr(self.lib, name)(*(int(v) for v in sizes), C.byref(need)), name)
+        return need.value
 
     def mpc_box_workspace(self, B: int, L: int, rows: int) -> torch.Tensor:
         """The caller-owned workspace of gym_mpc_box_qp (rows = stages given) / gym_mpc_box_rollout (rows = N)."""
-        need = C.c_int64()
-        _lib.check(self.lib.gym_mpc_box_workspace(int(B), int(L), int(rows), C.byref(need)), "gym_mpc_box_workspace")
-        return torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        return torch.empty(self._ws_bytes("gym_mpc_box_workspace", B, L, rows), dtype=torch.uint8, device=self.device)
 
     def mpc_box_qp(self, A, Bm, u_ref, Q, R, QT, x0, L: int, tau_max: float, max_qp_iters: int = 32, ws=None):
         """gym_mpc_box_qp: the torque-limited QP of one window for a batch x0 (B,4).  Stages A (S,4,4), Bm (S,4,2),
@@ -459,9 +451,7 @@ class AcrobotEngine:
         ur = np.ascontiguousarray(ur[:S])
         if np.any(Bm[:, :, 0] != 0.0):
             raise ValueError("the torque-limited QP needs B[:, 0] = 0 at every stage (channel 0 must separate)")
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
-        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
-            raise ValueError(f"the torque-limited QP needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
+        Qh, Rh = host_mat(Q, 4, "Q"), check_diagonal_R(R, "the torque-limited QP")
         QTd = self.t(QT).reshape(4, 4)
         x0 = self.t(x0).reshape(-1, 4)
         B = x0.shape[0]
@@ -491,7 +481,7 @@ class AcrobotEngine:
         if u_ref.shape[0] < N - 1:
             raise ValueError(f"u_ref must hold {N - 1} stages, got {u_ref.shape[0]}")
         L = K_all.shape[1] + 1
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
+        Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
         B = x0.shape[0]
         ws = self.mpc_box_workspace(B, L, N) if ws is None else ws
         x = torch.empty((B, N, 4), dtype=F64, device=self.device)
@@ -509,25 +499,15 @@ class AcrobotEngine:
     # ------------------------------------------------------------- per-lane LQR tracking
     def lqr_lanes_workspace(self, B: int, N: int) -> torch.Tensor:
         """The caller-owned workspace of gym_lqr_lanes_gains / gym_lqr_lanes_rollout for B lanes of N knots."""
-        need = C.c_int64()
-        _lib.check(self.lib.gym_lqr_lanes_workspace(int(B), int(N), C.byref(need)), "gym_lqr_lanes_workspace")
-        return torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        return torch.empty(self._ws_bytes("gym_lqr_lanes_workspace", B, N), dtype=torch.uint8, device=self.device)
 
     def lqr_lanes_gains(self, x_opt, u_opt, Q, R, QT, gains: bool = True, ws=None):
         """gym_lqr_lanes_gains: solve_LQR_tracking per lane along x_opt (B,N,4), u_opt (B,N-1,2).  Returns (ws, K):
         the filled workspace lqr_lanes_rollout takes, and K (B,N-1,2,4) on the device (None unless ``gains``)."""
         x_opt = self.t(x_opt); u_opt = self.t(u_opt)
-        if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
-            raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
-        B, N = x_opt.shape[0], x_opt.shape[1]
-        if tuple(u_opt.shape) != (B, N - 1, 2):
-            raise ValueError(f"u_opt must be ({B},{N - 1},2) for x_opt {tuple(x_opt.shape)}, got {tuple(u_opt.shape)}")
-        Qh, Rh, QTh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R"), self._host_mat(QT, 4, "QT")
-        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
-            raise ValueError(f"per-lane LQR tracking needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
-        for name, M in (("Q", Qh), ("QT", QTh)):
-            if not np.array_equal(M, M.T):
-                raise ValueError(f"{name} must be symmetric, got {M.tolist()}")
+        B, N = check_lane_trajectories(x_opt, u_opt)
+        Rh = check_diagonal_R(R, "per-lane LQR tracking")
+        Qh, QTh = check_sym_weight(Q, "Q"), check_sym_weight(QT, "QT")
         ws = self.lqr_lanes_workspace(B, N) if ws is None else ws
         K = torch.empty((B, N - 1, 2, 4), dtype=F64, device=self.device) if gains else None
         _lib.check(self.lib.gym_lqr_lanes_gains(C.byref(self.model), x_opt.data_ptr(), u_opt.data_ptr(), B, N,
@@ -539,8 +519,7 @@ class AcrobotEngine:
         """gym_lqr_lanes_rollout on a workspace lqr_lanes_gains filled: x0 (B,P,4) -> (x (B,P,N,4), u (B,P,N-1,2),
         summary (3,B,P) = err_final, err_max, u_max) on the device; x, u are None unless ``trajectories``."""
         x0 = self.t(x0)
-        if x0.ndim != 3 or x0.shape[2] != 4 or x0.shape[0] < 1 or x0.shape[1] < 1:
-            raise ValueError(f"x0 must be (B,P,4), got {tuple(x0.shape)}")
+        check_lane_starts(x0)
         B, P, N = x0.shape[0], x0.shape[1], int(N)
         x = torch.empty((B, P, N, 4), dtype=F64, device=self.device) if trajectories else None
         u = torch.empty((B, P, N - 1, 2), dtype=F64, device=self.device) if trajectories else None
@@ -557,29 +536,17 @@ class AcrobotEngine:
         read back.  Returns (ws, K): the filled lqr_lanes_workspace lqr_lanes_rollout takes, and K0 (B,N-1,2,4) on the
         device (None unless ``gains``)."""
         x_opt = self.t(x_opt); u_opt = self.t(u_opt)
-        if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
-            raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
-        B, N = x_opt.shape[0], x_opt.shape[1]
-        if tuple(u_opt.shape) != (B, N - 1, 2):
-            raise ValueError(f"u_opt must be ({B},{N - 1},2) for x_opt {tuple(x_opt.shape)}, got {tuple(u_opt.shape)}")
-        L = int(L)
-        if L < 2 or L + 2 > _lib.MPC_MAX_STAGES:
-            raise ValueError(f"T_pred must be in [2, {_lib.MPC_MAX_STAGES - 2}] for per-lane MPC tracking, got {L}")
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
-        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
-            raise ValueError(f"per-lane MPC tracking needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
-        if not np.array_equal(Qh, Qh.T):
-            raise ValueError(f"Q must be symmetric, got {Qh.tolist()}")
-        QTd = self.t(QT)
-        if tuple(QTd.shape) != (4, 4):
-            raise ValueError(f"QT must be (4,4), got {tuple(QTd.shape)}")
+        B, N = check_lane_trajectories(x_opt, u_opt)
+        L = check_window(L, "per-lane MPC tracking")
+        Rh = check_diagonal_R(R, "per-lane MPC tracking")
+        Qh = check_sym_weight(Q, "Q")
+        QTd = check_device_QT(self.t(QT))
+        need = self._ws_bytes("gym_lqr_lanes_workspace", B, N)
         if ws is None:
-            ws = self.lqr_lanes_workspace(B, N)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         ws_bytes = ws.numel() * ws.element_size()
-        need = C.c_int64()
-        _lib.check(self.lib.gym_lqr_lanes_workspace(B, N, C.byref(need)), "gym_lqr_lanes_workspace")
-        if ws_bytes < need.value:
-            raise ValueError(f"the workspace holds {ws_bytes} bytes, {B} lanes of {N} knots need {need.value}")
+        if ws_bytes < need:
+            raise ValueError(f"the workspace holds {ws_bytes} bytes, {B} lanes of {N} knots need {need}")
         K = torch.empty((B, N - 1, 2, 4), dtype=F64, device=self.device) if gains else None
         _lib.check(self.lib.gym_mpc_lanes_gains(C.byref(self.model), x_opt.data_ptr(), u_opt.data_ptr(), B, N, L,
                                                 Qh.ctypes.data, Rh.ctypes.data, QTd.data_ptr(), ws.data_ptr(),
@@ -591,10 +558,7 @@ class AcrobotEngine:
 
     def mpc_box_lanes_workspace(self, B: int, P: int, L: int) -> int:
         """Bytes of gym_mpc_box_lanes_rollout's caller-owned workspace for B lanes x P starts, windows of L stages."""
-        need = C.c_int64()
-        _lib.check(self.lib.gym_mpc_box_lanes_workspace(int(B), int(P), int(L), C.byref(need)),
-                   "gym_mpc_box_lanes_workspace")
-        return need.value
+        return self._ws_bytes("gym_mpc_box_lanes_workspace", B, P, L)
 
     def mpc_box_lanes_rollout(self, x_opt, u_opt, x0, Q, R, QT, L: int, tau_max: float, max_qp_iters: int = 32,
                               trajectories: bool = True, max_ws_bytes: int | None = None):
@@ -605,30 +569,15 @@ class AcrobotEngine:
         allocated here; a batch whose workspace would exceed ``max_ws_bytes`` (default: BOX_LANES_WS_SHARE of the free
         device memory) runs in chunks of whole lanes, one call each -- the same results, lanes being independent."""
         x_opt = self.t(x_opt); u_opt = self.t(u_opt); x0 = self.t(x0)
-        if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
-            raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
-        B, N = x_opt.shape[0], x_opt.shape[1]
-        if tuple(u_opt.shape) != (B, N - 1, 2):
-            raise ValueError(f"u_opt must be ({B},{N - 1},2) for x_opt {tuple(x_opt.shape)}, got {tuple(u_opt.shape)}")
-        if x0.ndim != 3 or x0.shape[0] != B or x0.shape[1] < 1 or x0.shape[2] != 4:
-            raise ValueError(f"x0 must be ({B},P,4), got {tuple(x0.shape)}")
-        P, L = x0.shape[1], int(L)
-        if L < 2 or L + 2 > _lib.MPC_MAX_STAGES:
-            raise ValueError(f"T_pred must be in [2, {_lib.MPC_MAX_STAGES - 2}] for the torque-limited QP, got {L}")
+        B, N = check_lane_trajectories(x_opt, u_opt)
+        check_lane_starts(x0, B)
+        P, L = x0.shape[1], check_window(L, "the torque-limited QP")
         if B * P > _lib.MAX_BP:
             raise ValueError(f"{B} lanes x {P} starts exceed {_lib.MAX_BP} closed loops per call")
-        if not (np.isfinite(tau_max) and tau_max > 0):
-            raise ValueError(f"tau_max must be finite and positive, got {tau_max}")
-        if int(max_qp_iters) < 1:
-            raise ValueError(f"max_qp_iters must be at least 1, got {max_qp_iters}")
-        Qh, Rh = self._host_mat(Q, 4, "Q"), self._host_mat(R, 2, "R")
-        if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
-            raise ValueError(f"the torque-limited QP needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
-        if not np.array_equal(Qh, Qh.T):
-            raise ValueError(f"Q must be symmetric, got {Qh.tolist()}")
-        QTd = self.t(QT)
-        if tuple(QTd.shape) != (4, 4):
-            raise ValueError(f"QT must be (4,4), got {tuple(QTd.shape)}")
+        check_box(tau_max, max_qp_iters)
+        Rh = check_diagonal_R(R, "the torque-limited QP")
+        Qh = check_sym_weight(Q, "Q")
+        QTd = check_device_QT(self.t(QT))
         per_lane = self.mpc_box_lanes_workspace(1, P, L)
         if max_ws_bytes is None:
             max_ws_bytes = int(self.BOX_LANES_WS_SHARE * torch.cuda.mem_get_info(self.device)[0])
@@ -651,3 +600,73 @@ class AcrobotEngine:
             if sm is not summary:
                 summary[:, b0:b1] = sm
         return x, u, summary, it, unconv
+
+
+# ------------------------------------------------------------------ the trackers' argument checks
+# Plain functions of shapes and host values (torch tensors and numpy arrays alike): no device, no engine, so the
+# front end (trajectory_tracking.py) refuses a bad call with the same words before it asks for either.
+def host_mat(M, n, name):
+    M = np.ascontiguousarray(np.asarray(M, dtype=np.float64))
+    if M.shape != (n, n):
+        raise ValueError(f"{name} must be {n}x{n}, got {M.shape}")
+    return M
+
+
+def check_lane_trajectories(x_opt, u_opt, or_n_rows: bool = False):
+    """Per-lane trajectories x_opt (B,N,4) with N >= 2 and u_opt (B,N-1,2); ``or_n_rows``: u_opt may hold N rows (the
+    caller trims the last, as newton_Algorithm trims u_ref).  Returns (B, N)."""
+    if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
+        raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
+    B, N = x_opt.shape[0], x_opt.shape[1]
+    if tuple(u_opt.shape) != (B, N - 1, 2) and not (or_n_rows and tuple(u_opt.shape) == (B, N, 2)):
+        raise ValueError(f"u_opt must be ({B},{N - 1},2){f' (or {N} rows)' if or_n_rows else ''} for x_opt "
+                         f"{tuple(x_opt.shape)}, got {tuple(u_opt.shape)}")
+    return B, N
+
+
+def check_lane_starts(x0, B: int | None = None, flat_ok: bool = False):
+    """Per-lane starts x0 (B,P,4) with P >= 1, for ``B`` lanes where it is given; ``flat_ok``: (B,4) passes too (the
+    caller adds the P axis)."""
+    lead = "B" if B is None else B
+    if not (x0.ndim == 3 and x0.shape[1] >= 1 or flat_ok and x0.ndim == 2) or x0.shape[-1] != 4 or (
+            x0.shape[0] < 1 if B is None else x0.shape[0] != B):
+        raise ValueError(f"x0 must be {f'({lead},4) or ' if flat_ok else ''}({lead},P,4), got {tuple(x0.shape)}")
+
+
+def check_diagonal_R(R, what: str) -> np.ndarray:
+    """The host R (2,2) of a tracker that splits the channels (``what`` names it): diagonal, R[1][1] finite and > 0."""
+    Rh = host_mat(R, 2, "R")
+    if Rh[0, 1] != 0.0 or Rh[1, 0] != 0.0 or not (np.isfinite(Rh[1, 1]) and Rh[1, 1] > 0):
+        raise ValueError(f"{what} needs a diagonal R with R[1][1] > 0, got {Rh.tolist()}")
+    return Rh
+
+
+def check_sym_weight(M, name: str) -> np.ndarray:
+    """The host weight ``name`` (4,4) of a per-lane tracker (their recursions keep the upper triangle only)."""
+    Mh = host_mat(M, 4, name)
+    if not np.array_equal(Mh, Mh.T):
+        raise ValueError(f"{name} must be symmetric, got {Mh.tolist()}")
+    return Mh
+
+
+def check_window(T_pred, what: str) -> int:
+    """The MPC window of the fused kernels (``what`` names the caller): T_pred + 2 stages fit one LDS table."""
+    L = int(T_pred)
+    if L < 2 or L + 2 > _lib.MPC_MAX_STAGES:
+        raise ValueError(f"T_pred must be in [2, {_lib.MPC_MAX_STAGES - 2}] for {what}, got {L}")
+    return L
+
+
+def check_box(tau_max, max_qp_iters):
+    """The torque limit and the active set's sweep cap."""
+    if not (np.isfinite(tau_max) and tau_max > 0):
+        raise ValueError(f"tau_max must be finite and positive, got {tau_max}")
+    if int(max_qp_iters) < 1:
+        raise ValueError(f"max_qp_iters must be at least 1, got {max_qp_iters}")
+
+
+def check_device_QT(QT):
+    """The terminal weight as a device tensor (mpc_gains' Q_T): (4,4)."""
+    if tuple(QT.shape) != (4, 4):
+        raise ValueError(f"QT must be (4,4), got {tuple(QT.shape)}")
+    return QT

@@ -1,8 +1,9 @@
 """Drop-in for the reference's ``trajectory_tracking`` module (LQR and receding-horizon MPC trackers).
 
 Reference: /root/reference/trajectory_tracking.py (main.py task_3 / task_4).  Same names, arguments and
-return values; the arithmetic runs in the gfx950 kernels of csrc/tracking_kernels.hip (gym_tv_lqr_gains,
-gym_dare_fixed_point, gym_lq_forward, gym_track_rollout) and the acrobot kernels (Jacobians, RK4).
+return values; the arithmetic runs in the gfx950 kernels of the csrc/tracking_kernels.hip translation unit
+(tracking_dense.hpp: gym_tv_lqr_gains, gym_dare_fixed_point, gym_lq_forward; mpc_gains.hpp: gym_mpc_gains;
+track_rollout.hpp: gym_track_rollout; mpc_box.hpp: the torque-limited QP) and the acrobot kernels (Jacobians, RK4).
 
 Without a torque limit (the reference's default, test_constraints = False, :87) the MPC QP (solver_mpc
 :73-140) has only equality constraints, so its solution is the finite-horizon LQ solution over the window; it
@@ -36,6 +37,7 @@ import torch
 
 from . import _lib
 from . import dynamics as _dyn
+from .engine import check_box, check_lane_starts, check_lane_trajectories, check_window
 from .dynamics import dt, ns, ni  # noqa: F401  (the reference module's namespace, trajectory_tracking.py:3)
 
 nu = ni
@@ -144,12 +146,7 @@ def _lane_trajectories(eng, x_opt, u_opt):
     (trajectory_generation.py:301-303), other mismatches raise."""
     x_opt = eng.t(x_opt)
     u_opt = eng.t(u_opt)
-    if x_opt.ndim != 3 or x_opt.shape[2] != 4 or x_opt.shape[1] < 2:
-        raise ValueError(f"x_opt must be (B,N,4) with N >= 2, got {tuple(x_opt.shape)}")
-    B, N = x_opt.shape[0], x_opt.shape[1]
-    if u_opt.ndim != 3 or u_opt.shape[2] != 2 or u_opt.shape[0] != B or u_opt.shape[1] not in (N - 1, N):
-        raise ValueError(f"u_opt must be ({B},{N - 1},2) (or {N} rows) for x_opt {tuple(x_opt.shape)}, "
-                         f"got {tuple(u_opt.shape)}")
+    B, N = check_lane_trajectories(x_opt, u_opt, or_n_rows=True)
     if u_opt.shape[1] == N:
         u_opt = u_opt[:, :N - 1].contiguous()
     return x_opt, u_opt
@@ -159,17 +156,22 @@ def _lane_starts(eng, x0, x_opt):
     """x0 (B,4) or (B,P,4) on the device as (B,P,4), and whether it came without the P axis."""
     B = x_opt.shape[0]
     x0 = eng.t(x0)
-    if x0.ndim not in (2, 3) or x0.shape[-1] != 4 or x0.shape[0] != B or (x0.ndim == 3 and x0.shape[1] < 1):
-        raise ValueError(f"x0 must be ({B},4) or ({B},P,4) for x_opt {tuple(x_opt.shape)}, got {tuple(x0.shape)}")
+    check_lane_starts(x0, B, flat_ok=True)
     return x0.reshape(B, -1, 4), x0.ndim == 2
 
 
+def _drop_starts_axis(flat, summary, *per_start):
+    """The outputs of a closed loop of x0 (B,P,4) for an x0 that came as (B,4) (``flat``): summary (3,B,P) and the
+    tensors (B,P,...) (or None) without the P axis again."""
+    if not flat:
+        return (summary, *per_start)
+    return (summary[:, :, 0], *(None if t is None else t[:, 0] for t in per_start))
+
+
 def _lane_rollout(eng, ws, x0, N, trajectories, flat):
-    """The closed loop of x0 (B,P,4) on a workspace a per-lane gains call filled (gym_lqr_lanes_rollout); ``flat``
-    drops the P axis again."""
+    """The closed loop of x0 (B,P,4) on a workspace a per-lane gains call filled (gym_lqr_lanes_rollout)."""
     x, u, s = eng.lqr_lanes_rollout(ws, x0, N, trajectories=trajectories)
-    if flat:
-        x, u, s = (None if x is None else x[:, 0]), (None if u is None else u[:, 0]), s[:, :, 0]
+    s, x, u = _drop_starts_axis(flat, s, x, u)
     return x, u, s
 
 
@@ -256,23 +258,18 @@ class MpcBoxLanesResult(MpcLanesResult):
 
 
 def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bool = True, T_pred: int = T_PRED,
-                       Q=Q_MPC, R=R_MPC, **limit) -> MpcLanesResult:
+                       Q=Q_MPC, R=R_MPC, tau_max=None, max_qp_iters: int = 32) -> MpcLanesResult:
     """Receding-horizon MPC tracking of every lane's OWN trajectory (main.py task_2's result into task_4, per lane;
     solve_mpc_tracking :8-69): lane b's first gains come from the T_pred-stage windows along (x_opt[b], u_opt[b]) and
     its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are simulated in closed loop against them.
     Shapes, ``trajectories`` and ``gains`` as LQR_tracking_lanes.
 
-    Two more keywords, ``tau_max=None`` and ``max_qp_iters=32``, are taken through ``**limit`` (the named keywords
-    above are a pinned part of the interface; any other name raises TypeError as an unknown keyword does).
     ``tau_max`` (None: the reference's default, no limit) is solver_mpc's torque limit (test_constraints, :87-114;
     the reference uses 18): every stage of every window obeys |u_opt[b][t] + u_t| <= tau_max, so every control step
     of every closed loop owns an inequality-constrained QP, solved by the active set of the shared-reference path
     (at most ``max_qp_iters`` sweeps each) in the kernel of csrc/mpc_box_lanes.hpp (gym_mpc_box_lanes_rollout; DESIGN
     4.7).  Returns an MpcBoxLanesResult then; where no bound is ever active its x, u and summaries are the
     unlimited call's bit for bit."""
-    tau_max, max_qp_iters = limit.pop("tau_max", None), limit.pop("max_qp_iters", 32)
-    if limit:
-        raise TypeError(f"MPC_tracking_lanes() got an unexpected keyword argument {sorted(limit)[0]!r}")
     if tau_max is not None:
         _check_box(tau_max, T_pred, max_qp_iters)
     eng = _eng()
@@ -286,9 +283,7 @@ def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bo
     K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=True)[1] if gains else None
     x, u, s, it, unconv = eng.mpc_box_lanes_rollout(x_opt, u_opt, x0, Q, R, QT, int(T_pred), float(tau_max),
                                                     int(max_qp_iters), trajectories=trajectories)
-    if flat:
-        x, u, it = (None if x is None else x[:, 0]), (None if u is None else u[:, 0]), (None if it is None else it[:, 0])
-        s, unconv = s[:, :, 0], unconv[:, 0]
+    s, x, u, it, unconv = _drop_starts_axis(flat, s, x, u, it, unconv)
     return MpcBoxLanesResult(x, u, K, s[0], s[1], s[2], QT.clone(), unconv, it)
 
 
@@ -313,12 +308,9 @@ class MpcBoxResult:
 
 
 def _check_box(tau_max, T_pred, max_qp_iters):
-    if not (np.isfinite(tau_max) and tau_max > 0):
-        raise ValueError(f"tau_max must be finite and positive, got {tau_max}")
-    if int(T_pred) < 2 or int(T_pred) + 2 > MPC_FUSED_MAX_STAGES:
-        raise ValueError(f"T_pred must be in [2, {MPC_FUSED_MAX_STAGES - 2}] for the torque-limited QP, got {T_pred}")
-    if int(max_qp_iters) < 1:
-        raise ValueError(f"max_qp_iters must be at least 1, got {max_qp_iters}")
+    """The torque-limited paths' arguments, refused before any device is needed (the engine's own checks)."""
+    check_box(tau_max, max_qp_iters)
+    check_window(T_pred, "the torque-limited QP")
 
 
 def solve_mpc_tracking_box_batch(x0, x_ref, u_ref, tau_max: float = TAU_MAX, T_pred: int = T_PRED,
@@ -344,12 +336,12 @@ def solve_mpc_tracking(x0, x_ref, u_ref, T, T_pred: int = T_PRED, tau_max=None):
     steps = int(T) - 1
     x_real = np.zeros(x_ref.shape)
     u_real = np.zeros(u_ref.shape)
+    x0 = np.asarray(x0, dtype=float).reshape(1, 4)
     if tau_max is not None:
-        res = solve_mpc_tracking_box_batch(np.asarray(x0, dtype=float).reshape(1, 4), x_ref, u_ref, tau_max, T_pred)
-        x_real[:steps + 1] = _np(res.x[0])[:steps + 1]
-        u_real[:steps] = _np(res.u[0])[:steps]
-        return x_real, u_real
-    x, u, _ = solve_mpc_tracking_batch(np.asarray(x0, dtype=float).reshape(1, 4), x_ref, u_ref, T_pred)
+        res = solve_mpc_tracking_box_batch(x0, x_ref, u_ref, tau_max, T_pred)
+        x, u = res.x, res.u
+    else:
+        x, u, _ = solve_mpc_tracking_batch(x0, x_ref, u_ref, T_pred)
     x_real[:steps + 1] = _np(x[0])[:steps + 1]
     u_real[:steps] = _np(u[0])[:steps]
     return x_real, u_real

@@ -40,7 +40,7 @@ def test_python_surface():
         assert hasattr(obj, n), n
     sig = inspect.signature(tt.MPC_tracking_lanes)
     assert [p for p, v in sig.parameters.items() if v.kind is v.KEYWORD_ONLY] == ["trajectories", "gains", "T_pred",
-                                                                                  "Q", "R"]
+                                                                                  "Q", "R", "tau_max", "max_qp_iters"]
     assert list(inspect.signature(AcrobotEngine.mpc_lanes_gains).parameters) == [
         "self", "x_opt", "u_opt", "Q", "R", "QT", "L", "gains", "ws"]
     lqr = [f for f in tt.LqrLanesResult.__dataclass_fields__]

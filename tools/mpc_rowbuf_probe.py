@@ -4,7 +4,7 @@
 Round 3 unrolled k_track_rollout_pair's step loop by two with two register sets of the per-step feedback rows (K,
 x_ff, u_ff), so that no row is copied between steps; that build failed the pair-vs-single-lane bitwise test and was
 reverted without a diagnosis.  This probe rebuilds the variant from the committed kernel (a patched copy of
-tracking_kernels.hip in a scratch directory) and tells the two candidate causes apart:
+csrc/track_rollout.hpp in a scratch directory) and tells the two candidate causes apart:
 
   * FMA contraction: the feedback u = u_ff + K (x - x_ff) is compiled under the file's default -ffp-contract=fast,
     so the backend picks which product of ((k0 d0 + k1 d1) + k2 d2) + k3 d3 it fuses, per code context.  --isa
@@ -33,6 +33,7 @@ sys.path.insert(0, ROOT)
 CSRC = os.path.join(ROOT, "gymnast_optimalcontrol_amd", "csrc")
 OUT = os.path.join(ROOT, "build_ab")
 
+KERNEL_FILE = "track_rollout.hpp"      # the header of the tracking_kernels.hip unit that holds both rollout kernels
 LOOP_COMMITTED = "    for (int t = 0; t < T; ++t) {\n        const double d0 = n0 - r[0]"
 
 VARIANT_LOOP = r'''    double kB[8], rB[4], fB[2];
@@ -69,10 +70,10 @@ INLINE_FAST_BODY = """        const double v0 = f[0] + (((k[0] * d0 + k[1] * d1)
 
 
 def patched_source(variant: bool, fast: bool) -> str:
-    """The committed tracking_kernels.hip (feedback through track_feedback, contract(on)); ``fast``: the feedback
+    """The committed track_rollout.hpp (feedback through track_feedback, contract(on)); ``fast``: the feedback
     inlined under the file's default -ffp-contract=fast, as before the fix; ``variant``: the pair rollout's loop
     unrolled by two with double-buffered rows (round 3's reverted build)."""
-    s = open(os.path.join(CSRC, "tracking_kernels.hip")).read()
+    s = open(os.path.join(CSRC, KERNEL_FILE)).read()
     if fast:
         assert s.count(INLINE_FAST) == 2
         s = s.replace(INLINE_FAST, INLINE_FAST_BODY)
@@ -94,7 +95,7 @@ def build(name: str, variant: bool, fast: bool) -> str:
     tmp = tempfile.mkdtemp(prefix="gym_probe_")
     for f in os.listdir(CSRC):
         shutil.copy(os.path.join(CSRC, f), tmp)
-    open(os.path.join(tmp, "tracking_kernels.hip"), "w").write(patched_source(variant, fast))
+    open(os.path.join(tmp, KERNEL_FILE), "w").write(patched_source(variant, fast))
     os.makedirs(OUT, exist_ok=True)
     out = os.path.join(OUT, name)
     cmd = [_build.hipcc(), f"--offload-arch={_build.ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
