@@ -1,0 +1,137 @@
+"""What a batched Newton solve returns and what it continues from: SolveResult (with its .npz writer and the
+tracking front ends on its lanes), Checkpoint and load_checkpoint.  Host I/O and dataclasses only."""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import _lib
+from .params import DT
+
+
+@dataclass
+class SolveResult:
+    x: torch.Tensor          # (B,N,4)
+    u: torch.Tensor          # (B,T,2)
+    K: torch.Tensor          # (B,T,2,4)  gains of each lane's last iteration
+    sigma: torch.Tensor      # (B,T,2)
+    cost: torch.Tensor       # (B,)
+    n_iter: torch.Tensor     # (B,) outer iterations executed (incl. a final failed one)
+    status: torch.Tensor     # (B,) _lib.CONVERGED / LS_FAILED / MAX_ITERS
+    n_rollouts: torch.Tensor # (B,)
+    gamma: torch.Tensor      # (B,) last accepted step
+    iterations: int          # outer loop iterations run for the whole batch
+    lane_iterations: int     # sum of n_iter over lanes (the throughput numerator)
+    seconds: float           # wall time of the solve loop (init + iterations + finalize)
+    stats_log: list = field(default_factory=list)
+    hist_cost: torch.Tensor | None = None   # (hist_len, B)
+    hist_smax: torch.Tensor | None = None   # (hist_len, B)
+    x_trajs: dict | None = None             # {lane: [x_0, x_1, ...]} of the captured lanes (capture_lanes)
+    cost0: dict | None = None               # {lane: J_0} of the captured lanes
+    sigmas: dict | None = None              # {lane: {iteration: sigma (T,2)}} of the captured lanes (capture_sigma)
+    schedule: str = ""                      # "serial" | "pipelined" | "persistent"
+    tail_lane_iterations: int = 0           # lane-iterations run by the straggler tail (gym_newton_tail)
+    compactions: int = 0                    # lane compactions during the loop (BatchedNewtonSolver.compact)
+    lowocc_lane_iterations: int = 0         # lane-iterations run in the low-occupancy regime (maybe_compact)
+    tail_from_iteration: int | None = None  # the outer iteration the straggler tail took over at (None: no tail)
+    tail_iterations: int = 0                # outer iterations the tail ran (its slowest lane's, up to the last one)
+
+    def save_npz(self, path, t=None, dt: float = DT):
+        """Write the per-lane results as one .npz in the reference's wire format (main.py:74-79, np.savez(x=, u=,
+        t=)): x (B,N,4), u (B,T,2), t (N,) = arange(N) * dt unless given, plus cost, status, n_iter, gamma,
+        n_rollouts, K and sigma, which load_checkpoint / BatchedNewtonSolver.resume continue from.  Host I/O only:
+        tensors on any device."""
+        a = {k: getattr(self, k).detach().cpu().numpy() for k in CHECKPOINT_KEYS}
+        N = a["x"].shape[1]
+        a["t"] = np.arange(N) * float(dt) if t is None else np.asarray(t, dtype=np.float64)
+        if a["t"].shape != (N,):
+            raise ValueError(f"t must hold the {N} knot times, got {a['t'].shape}")
+        np.savez(path, **a)
+
+    def _track_starts(self, x0, dx0):
+        """The perturbed starts of track_lqr / track_mpc: x0 itself, or x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4)
+        (default: no perturbation)."""
+        if x0 is not None and dx0 is not None:
+            raise ValueError("give x0 or dx0, not both")
+        if x0 is not None:
+            return x0
+        start = self.x[:, 0]
+        if dx0 is None:
+            return start
+        d = torch.as_tensor(np.asarray(dx0.detach().cpu() if isinstance(dx0, torch.Tensor) else dx0, dtype=np.float64),
+                            device=start.device)
+        B = start.shape[0]
+        if tuple(d.shape) == (4,) or tuple(d.shape) == (B, 4):
+            return start + d
+        if d.ndim == 3 and d.shape[0] == B and d.shape[2] == 4:
+            return start[:, None, :] + d
+        raise ValueError(f"dx0 must be (4,), ({B},4) or ({B},P,4), got {tuple(d.shape)}")
+
+    def track_lqr(self, x0=None, dx0=None, **kw):
+        """LQR tracking of every lane's own result (trajectory_tracking.LQR_tracking_lanes on this result's x, u):
+        x0 (B,4) or (B,P,4) perturbed starts, default x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4) (default: no
+        perturbation).  Keyword arguments go to LQR_tracking_lanes.  Returns its LqrLanesResult."""
+        from . import trajectory_tracking as tt
+        return tt.LQR_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
+
+    def track_mpc(self, x0=None, dx0=None, **kw):
+        """Receding-horizon MPC tracking of every lane's own result (trajectory_tracking.MPC_tracking_lanes on this
+        result's x, u); x0 / dx0 as track_lqr.  Keyword arguments (T_pred, Q, R, trajectories, gains, tau_max,
+        max_qp_iters) go to MPC_tracking_lanes.  Returns its MpcLanesResult; with a torque limit (``tau_max=18`` is the
+        reference's) every lane's closed loop keeps |u| <= tau_max and the result is an MpcBoxLanesResult."""
+        from . import trajectory_tracking as tt
+        return tt.MPC_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
+
+
+CHECKPOINT_KEYS = ("x", "u", "cost", "status", "n_iter", "gamma", "n_rollouts", "K", "sigma")
+
+
+@dataclass
+class Checkpoint:
+    """Per-lane iterates to continue from (load_checkpoint): SolveResult's per-lane fields and the knot times."""
+    x: torch.Tensor          # (B,N,4)
+    u: torch.Tensor          # (B,T,2)
+    t: torch.Tensor          # (N,)
+    cost: torch.Tensor       # (B,)   NaN where the file had none
+    status: torch.Tensor     # (B,)   int32
+    n_iter: torch.Tensor     # (B,)   int32
+    gamma: torch.Tensor      # (B,)
+    n_rollouts: torch.Tensor # (B,)   int32
+    K: torch.Tensor          # (B,T,2,4)
+    sigma: torch.Tensor      # (B,T,2)
+
+
+def load_checkpoint(path, device="cpu") -> Checkpoint:
+    """Read a checkpoint written by SolveResult.save_npz -- or a trajectory file of the reference itself
+    (acrobot_optimal_trajectory.npz: x (N,4), u (N-1 or N,2) without a lane axis, t, nothing else), which loads as a
+    one-lane checkpoint with the lane ACTIVE, n_iter = 0 and no gains.  Tensors go to ``device``."""
+    with np.load(path) as d:
+        a = {k: d[k] for k in d.files}
+    for k in ("x", "u"):
+        if k not in a:
+            raise ValueError(f"{path}: not a trajectory file (no '{k}')")
+    x, u = np.asarray(a["x"], dtype=np.float64), np.asarray(a["u"], dtype=np.float64)
+    if x.ndim == 2 and u.ndim == 2:
+        x, u = x[None], u[None]
+    if x.ndim != 3 or x.shape[2] != 4 or u.ndim != 3 or u.shape[2] != 2 or u.shape[0] != x.shape[0]:
+        raise ValueError(f"{path}: x {x.shape} / u {u.shape} are not (B,N,4) / (B,T,2) trajectories")
+    B, N = x.shape[:2]
+    if u.shape[1] == N:          # a control row per knot: the last one is unused (trajectory_generation.py:301-303)
+        u = u[:, :-1]
+    if u.shape[1] != N - 1:
+        raise ValueError(f"{path}: x has {N} knots but u has {u.shape[1]} controls (expected {N - 1})")
+    T = N - 1
+    full = {"x": x, "u": np.ascontiguousarray(u),
+            "t": np.asarray(a["t"], dtype=np.float64) if "t" in a else np.arange(N) * DT,
+            "cost": np.full(B, np.nan), "status": np.full(B, _lib.ACTIVE, np.int32), "n_iter": np.zeros(B, np.int32),
+            "gamma": np.zeros(B), "n_rollouts": np.zeros(B, np.int32), "K": np.zeros((B, T, 2, 4)),
+            "sigma": np.zeros((B, T, 2))}
+    for k in CHECKPOINT_KEYS[2:]:
+        if k in a:
+            v = np.asarray(a[k], dtype=full[k].dtype)
+            if v.shape != full[k].shape:
+                raise ValueError(f"{path}: '{k}' has shape {v.shape}, expected {full[k].shape}")
+            full[k] = v
+    return Checkpoint(**{k: torch.as_tensor(v).to(device) for k, v in full.items()})

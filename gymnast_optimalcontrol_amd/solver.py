@@ -24,191 +24,27 @@ task-2 reference) the unactuated tau1 controls are identically zero and their pl
 
 Multi-GPU: one process per GPU, each owning a contiguous shard of lanes; the only cross-GPU
 traffic is one all-reduce (SUM) of the 8 per-iteration statistics (see distributed.py).
+
+This file holds the solver; what a solve returns and continues from is results.py, the host loops host_loop.py,
+placement selection and its pool placement.py.
 """
 from __future__ import annotations
 
 import ctypes as C
 import time
-import weakref
-from collections import OrderedDict
-from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, placement
 from .engine import AcrobotEngine, padded, F64
-from .params import DT, MAX_LINE_SEARCH_ITERS
+from .host_loop import STAT_FIELDS, morton_order, newton_loop, run_loop, tail_loop  # noqa: F401
+from .params import MAX_LINE_SEARCH_ITERS
+from .placement import PlacementPool
+from .results import CHECKPOINT_KEYS, Checkpoint, SolveResult, load_checkpoint  # noqa: F401
 
-STAT_FIELDS = ("n_active", "sum_cost", "sum_smax2", "lanes_ran", "n_retry", "n_converged", "n_failed", "n_rollouts")
-
-
-@dataclass
-class SolveResult:
-    x: torch.Tensor          # (B,N,4)
-    u: torch.Tensor          # (B,T,2)
-    K: torch.Tensor          # (B,T,2,4)  gains of each lane's last iteration
-    sigma: torch.Tensor      # (B,T,2)
-    cost: torch.Tensor       # (B,)
-    n_iter: torch.Tensor     # (B,) outer iterations executed (incl. a final failed one)
-    status: torch.Tensor     # (B,) _lib.CONVERGED / LS_FAILED / MAX_ITERS
-    n_rollouts: torch.Tensor # (B,)
-    gamma: torch.Tensor      # (B,) last accepted step
-    iterations: int          # outer loop iterations run for the whole batch
-    lane_iterations: int     # sum of n_iter over lanes (the throughput numerator)
-    seconds: float           # wall time of the solve loop (init + iterations + finalize)
-    stats_log: list = field(default_factory=list)
-    hist_cost: torch.Tensor | None = None   # (hist_len, B)
-    hist_smax: torch.Tensor | None = None   # (hist_len, B)
-    x_trajs: dict | None = None             # {lane: [x_0, x_1, ...]} of the captured lanes (capture_lanes)
-    cost0: dict | None = None               # {lane: J_0} of the captured lanes
-    sigmas: dict | None = None              # {lane: {iteration: sigma (T,2)}} of the captured lanes (capture_sigma)
-    schedule: str = ""                      # "serial" | "pipelined" | "persistent"
-    tail_lane_iterations: int = 0           # lane-iterations run by the straggler tail (gym_newton_tail)
-    compactions: int = 0                    # lane compactions during the loop (BatchedNewtonSolver.compact)
-    lowocc_lane_iterations: int = 0         # lane-iterations run in the low-occupancy regime (maybe_compact)
-    tail_from_iteration: int | None = None  # the outer iteration the straggler tail took over at (None: no tail)
-    tail_iterations: int = 0                # outer iterations the tail ran (its slowest lane's, up to the last one)
-
-    def save_npz(self, path, t=None, dt: float = DT):
-        """Write the per-lane results as one .npz in the reference's wire format (main.py:74-79, np.savez(x=, u=,
-        t=)): x (B,N,4), u (B,T,2), t (N,) = arange(N) * dt unless given, plus cost, status, n_iter, gamma,
-        n_rollouts, K and sigma, which load_checkpoint / BatchedNewtonSolver.resume continue from.  Host I/O only:
-        tensors on any device."""
-        a = {k: getattr(self, k).detach().cpu().numpy() for k in CHECKPOINT_KEYS}
-        N = a["x"].shape[1]
-        a["t"] = np.arange(N) * float(dt) if t is None else np.asarray(t, dtype=np.float64)
-        if a["t"].shape != (N,):
-            raise ValueError(f"t must hold the {N} knot times, got {a['t'].shape}")
-        np.savez(path, **a)
-
-    def _track_starts(self, x0, dx0):
-        """The perturbed starts of track_lqr / track_mpc: x0 itself, or x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4)
-        (default: no perturbation)."""
-        if x0 is not None and dx0 is not None:
-            raise ValueError("give x0 or dx0, not both")
-        if x0 is not None:
-            return x0
-        start = self.x[:, 0]
-        if dx0 is None:
-            return start
-        d = torch.as_tensor(np.asarray(dx0.detach().cpu() if isinstance(dx0, torch.Tensor) else dx0, dtype=np.float64),
-                            device=start.device)
-        B = start.shape[0]
-        if tuple(d.shape) == (4,) or tuple(d.shape) == (B, 4):
-            return start + d
-        if d.ndim == 3 and d.shape[0] == B and d.shape[2] == 4:
-            return start[:, None, :] + d
-        raise ValueError(f"dx0 must be (4,), ({B},4) or ({B},P,4), got {tuple(d.shape)}")
-
-    def track_lqr(self, x0=None, dx0=None, **kw):
-        """LQR tracking of every lane's own result (trajectory_tracking.LQR_tracking_lanes on this result's x, u):
-        x0 (B,4) or (B,P,4) perturbed starts, default x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4) (default: no
-        perturbation).  Keyword arguments go to LQR_tracking_lanes.  Returns its LqrLanesResult."""
-        from . import trajectory_tracking as tt
-        return tt.LQR_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
-
-    def track_mpc(self, x0=None, dx0=None, **kw):
-        """Receding-horizon MPC tracking of every lane's own result (trajectory_tracking.MPC_tracking_lanes on this
-        result's x, u); x0 / dx0 as track_lqr.  Keyword arguments (T_pred, Q, R, trajectories, gains, tau_max,
-        max_qp_iters) go to MPC_tracking_lanes.  Returns its MpcLanesResult; with a torque limit (``tau_max=18`` is the
-        reference's) every lane's closed loop keeps |u| <= tau_max and the result is an MpcBoxLanesResult."""
-        from . import trajectory_tracking as tt
-        return tt.MPC_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
-
-
-CHECKPOINT_KEYS = ("x", "u", "cost", "status", "n_iter", "gamma", "n_rollouts", "K", "sigma")
-
-
-@dataclass
-class Checkpoint:
-    """Per-lane iterates to continue from (load_checkpoint): SolveResult's per-lane fields and the knot times."""
-    x: torch.Tensor          # (B,N,4)
-    u: torch.Tensor          # (B,T,2)
-    t: torch.Tensor          # (N,)
-    cost: torch.Tensor       # (B,)   NaN where the file had none
-    status: torch.Tensor     # (B,)   int32
-    n_iter: torch.Tensor     # (B,)   int32
-    gamma: torch.Tensor      # (B,)
-    n_rollouts: torch.Tensor # (B,)   int32
-    K: torch.Tensor          # (B,T,2,4)
-    sigma: torch.Tensor      # (B,T,2)
-
-
-def load_checkpoint(path, device="cpu") -> Checkpoint:
-    """Read a checkpoint written by SolveResult.save_npz -- or a trajectory file of the reference itself
-    (acrobot_optimal_trajectory.npz: x (N,4), u (N-1 or N,2) without a lane axis, t, nothing else), which loads as a
-    one-lane checkpoint with the lane ACTIVE, n_iter = 0 and no gains.  Tensors go to ``device``."""
-    with np.load(path) as d:
-        a = {k: d[k] for k in d.files}
-    for k in ("x", "u"):
-        if k not in a:
-            raise ValueError(f"{path}: not a trajectory file (no '{k}')")
-    x, u = np.asarray(a["x"], dtype=np.float64), np.asarray(a["u"], dtype=np.float64)
-    if x.ndim == 2 and u.ndim == 2:
-        x, u = x[None], u[None]
-    if x.ndim != 3 or x.shape[2] != 4 or u.ndim != 3 or u.shape[2] != 2 or u.shape[0] != x.shape[0]:
-        raise ValueError(f"{path}: x {x.shape} / u {u.shape} are not (B,N,4) / (B,T,2) trajectories")
-    B, N = x.shape[:2]
-    if u.shape[1] == N:          # a control row per knot: the last one is unused (trajectory_generation.py:301-303)
-        u = u[:, :-1]
-    if u.shape[1] != N - 1:
-        raise ValueError(f"{path}: x has {N} knots but u has {u.shape[1]} controls (expected {N - 1})")
-    T = N - 1
-    full = {"x": x, "u": np.ascontiguousarray(u),
-            "t": np.asarray(a["t"], dtype=np.float64) if "t" in a else np.arange(N) * DT,
-            "cost": np.full(B, np.nan), "status": np.full(B, _lib.ACTIVE, np.int32), "n_iter": np.zeros(B, np.int32),
-            "gamma": np.zeros(B), "n_rollouts": np.zeros(B, np.int32), "K": np.zeros((B, T, 2, 4)),
-            "sigma": np.zeros((B, T, 2))}
-    for k in CHECKPOINT_KEYS[2:]:
-        if k in a:
-            v = np.asarray(a[k], dtype=full[k].dtype)
-            if v.shape != full[k].shape:
-                raise ValueError(f"{path}: '{k}' has shape {v.shape}, expected {full[k].shape}")
-            full[k] = v
-    return Checkpoint(**{k: torch.as_tensor(v).to(device) for k, v in full.items()})
-
-
-class PlacementPool:
-    """Process-wide cache of the stream-buffer sets that placement selection chose (BatchedNewtonSolver._placement_*),
-    keyed by (device index, stream shapes).  A solver that chose a set leases it; when the solver is garbage-collected
-    the set comes back here, and the next solver of the same shape takes it without a probe or an allocation (the
-    batched newton_Algorithm builds a solver per call, bench.py one per leg).  At most one free set per key; free sets
-    beyond MAX_SHARE of the device's memory are dropped, oldest first.  ``clear()`` returns every free set to the
-    device."""
-    MAX_SHARE = 0.35
-    _free: "OrderedDict" = OrderedDict()
-
-    @staticmethod
-    def _bytes(key) -> int:
-        return 8 * sum(int(np.prod(sh)) for sh in key[1])
-
-    @classmethod
-    def take(cls, key):
-        """(streams, record) of a free set for ``key``, now leased to the caller, or None."""
-        return cls._free.pop(key, None)
-
-    @classmethod
-    def put(cls, key, streams, record):
-        if key in cls._free:
-            return
-        cls._free[key] = (streams, record)
-        try:
-            cap = cls.MAX_SHARE * torch.cuda.get_device_properties(key[0]).total_memory
-        except Exception:
-            return
-        while len(cls._free) > 1 and sum(cls._bytes(k) for k in cls._free) > cap:
-            cls._free.popitem(last=False)
-
-    @classmethod
-    def clear(cls):
-        cls._free.clear()
-        if torch.cuda.is_available():
-            torch.cuda.empty_cache()
-
-    @classmethod
-    def held_bytes(cls) -> int:
-        return sum(cls._bytes(k) for k in cls._free)
+# _launch arguments of a size query: plain sizes in, a count out; no structure, no stream
+_SIZES = dict(model=False, batch=False, stream=False)
 
 
 class BatchedNewtonSolver:
@@ -230,16 +66,10 @@ class BatchedNewtonSolver:
     # pipelined loop once at most this many lanes per CU (of all ranks) are still active: one wavefront per lane, so up
     # to one per SIMD it runs each lane's iteration at the latency of one sweep pass plus one trial chain.
     TAIL_LANES_PER_CU = 4
-    # Placement selection (see PlacementPool, _arm_placement and _placement_tick): the phase kernel's speed depends on
-    # where its six stream buffers land (1.89-2.08 ms per launch for sets alive at once in one process, each stable for
-    # its lifetime; profiles/r05/placement/, profiles/r06/README.md).  A large pipelined solver allocates up to
-    # PLACEMENT_CANDIDATES stream sets (as free memory allows), ranks them at construction with the placement probe
-    # (gym_placement_probe: the phase kernel's traffic without arithmetic, ~2 ms a launch; it ranks sets as the kernel
-    # does, Pearson 0.87-0.93), keeps the PLACEMENT_TRIALS best, and races those in its first solve: blocks of
-    # PLACEMENT_BLOCK iterations of that solve on each (the live state copied from set to set between blocks: the same
-    # bits on any set), the fastest kept.  In the zero-arithmetic probe about a third of the sets are fast (1.84-1.86
-    # ms), a third middling (1.95-2.03), the rest slow: eight candidates leave one selection in ~25 without a fast set,
-    # four one in 5 (profiles/r06/layout/).
+    # Placement selection (placement.py says why and how): up to PLACEMENT_CANDIDATES stream sets are ranked at
+    # construction, the PLACEMENT_TRIALS best raced in the first solve in blocks of PLACEMENT_BLOCK iterations; the
+    # extra sets take at most PLACEMENT_MEM_SHARE of the device.  Eight candidates leave one selection in ~25 without
+    # a fast set, four one in 5 (profiles/r06/layout/).
     PLACEMENT_CANDIDATES = 8
     PLACEMENT_TRIALS = 3
     PLACEMENT_MEM_SHARE = 0.45
@@ -268,16 +98,41 @@ class BatchedNewtonSolver:
                  arena=False, placement_trials: int | None = None):
         if B <= 0:
             raise ValueError("batch must hold at least one lane")
-        # the automatic schedule choice is made on ``schedule_lanes`` (default: this batch).  Sharded solves pass
-        # the largest shard of the global batch, so that every rank picks the same schedule: the schedules
-        # synchronise (all-reduce) at different points, and mixed choices would pair up the wrong collectives.
-        sched_B = self.B_sched = int(schedule_lanes) if schedule_lanes is not None else int(B)
-        auto_schedule = pipeline is None and persistent is None
         engine.weights.require_gain_solvable()
         self.eng = engine
-        self.x_ref, self.u_ref = engine.refs(x_ref, u_ref, per_lane=True)
+        self._set_refs(x_ref, u_ref, B, checkpoint)
+        self.armijo = _lib.GymArmijo(float(tol), float(beta), float(c), float(gamma_0), int(max_ls),
+                                     1 if hist_len > 0 else 0)
+        if max_ls < 1:
+            raise ValueError("max_ls must be >= 1")
+        self._set_u0_flag(u0_zero)
+        auto_schedule = pipeline is None and persistent is None
+        self._choose_schedule(pipeline, persistent, schedule_lanes, checkpoint, chunk, reorder, split_waves)
+        self._set_capture(capture_lanes, capture_every, capture_sigma)
+        st, placement_trials = self._alloc_streams(arena, placement_trials, auto_schedule)
+        self._alloc_lane_buffers(max_ls, hist_len)
+        self._fill_batch()
+        self._set_streams(st)
+        self._set_eligibility(auto_schedule, tail_lanes, tail_chunk, compact, world_size, cand_slots)
+        self.k, self.max_iters, self.lane_order = 0, None, None
+        self.lane_order_live = False   # True inside solve(), whose results follow lane_order back
+        self._serial_now = self._run_now = False
+        self.timeline = None    # diagnostics: a list records (iterations, active lanes, host time) per sync
+        self.timing = None
+        self.launches = {"phase": 0, "run": 0, "tail": 0, "iteration": 0}   # launches since reset_timing()
+        self._reset_solve_counters()
+        if self.placement is not None:            # a pooled set: back to the pool when this solver goes
+            placement.lease(self, self._pool_key, self.placement)
+        elif placement_trials > 1 and self.pipeline and not self.persistent:
+            self._arm_placement(placement_trials)
+
+    # --- the steps of __init__ -------------------------------------------------------------
+    def _set_refs(self, x_ref, u_ref, B, checkpoint):
+        """The references on the device and the batch's sizes B, Bp, N, T."""
+        self.x_ref, self.u_ref = self.eng.refs(x_ref, u_ref, per_lane=True)
         self.B, self.Bp = int(B), padded(int(B))
         self.N = int(self.x_ref.shape[-2])
+        self.T = self.N - 1
         # per-lane references (x_ref (B,N,4), u_ref (B,T,2); GYM_FLAG_REF_LANE): every schedule, no state
         # checkpointing
         self.ref_lane = self.x_ref.ndim == 3
@@ -290,58 +145,8 @@ class BatchedNewtonSolver:
             self._xr_in, self._ur_in = self.x_ref, self.u_ref
             self.xr_buf = torch.cat([self.x_ref, self.x_ref[-1:].expand(pad, -1, -1)]).contiguous()
             self.ur_buf = torch.cat([self.u_ref, self.u_ref[-1:].expand(pad, -1, -1)]).contiguous()
-        self.T = self.N - 1
-        self.armijo = _lib.GymArmijo(float(tol), float(beta), float(c), float(gamma_0), int(max_ls),
-                                     1 if hist_len > 0 else 0)
-        if max_ls < 1:
-            raise ValueError("max_ls must be >= 1")
-        dev = engine.device
-        e = lambda *s, dt=F64: torch.empty(s, dtype=dt, device=dev)  # noqa: E731
-        Bp, N, T = self.Bp, self.N, self.T
-        shapes = [(N, 2, Bp, 2), (N, 2, Bp, 2), (T, 2, Bp, 1), (T, 2, Bp, 1), (T, 2, Bp, 2), (T, 2, Bp, 1)]
-        self.pipeline = (sched_B >= self.pipeline_min_lanes(dev)) if pipeline is None else bool(pipeline)
-        # placement selection: default for the automatic schedule's pipelined solvers (the only schedule whose
-        # throughput is the HBM streams'); a set chosen by an earlier solver of this shape in this process is reused
-        # from the PlacementPool without a probe
-        if placement_trials is None:
-            placement_trials = (self.PLACEMENT_TRIALS if (auto_schedule and self.pipeline and persistent is not True
-                                                          and not arena and not checkpoint) else 1)
-        self.placement = None
-        self._pl = None
-        self._pool_key = (torch.device(dev).index, tuple(shapes))
-        pooled = PlacementPool.take(self._pool_key) if int(placement_trials) > 1 and not arena else None
-        if pooled is not None:
-            st, rec = pooled
-            self.placement = dict(rec, reused=True)
-        elif arena:
-            # the six streams carved from one allocation, each 2 MiB aligned, in this order (arena: True = a torch
-            # allocation, or a callable n -> fp64 device tensor of n elements that provides it)
-            al = (2 << 20) // 8
-            offs, n = [], 0
-            for sh in shapes:
-                offs.append(n)
-                n += -(-int(np.prod(sh)) // al) * al
-            self._arena = arena(n) if callable(arena) else e(n)
-            st = [self._arena[o:o + int(np.prod(sh))].view(sh) for o, sh in zip(offs, shapes)]
-        else:
-            st = [e(*sh) for sh in shapes]
-        self._stream_shapes = shapes
-        self._set_streams(st)
-        self.cost, self.dJ, self.smax, self.gamma = e(Bp), e(Bp), e(Bp), e(Bp)
-        i32 = torch.int32
-        self.status, self.n_iter, self.res_buf, self.n_roll = (e(Bp, dt=i32) for _ in range(4))
-        self.retry_list = e(Bp, dt=i32)
-        self.counters = torch.zeros(4, dtype=i32, device=dev)
-        self.cand_ok = torch.zeros((max(int(max_ls), 1), Bp), dtype=torch.uint8, device=dev)
-        self.partials = e(256 * 8)
-        self.stats = torch.zeros(24, dtype=F64, device=dev)     # [0,8) totals, [8,16) / [16,24) halves
-        self.max_iters = None
-        self.hist_len = int(hist_len)
-        self.hist_cost = torch.full((hist_len, Bp), float("nan"), dtype=F64, device=dev) if hist_len else None
-        self.hist_smax = torch.full((hist_len, Bp), float("nan"), dtype=F64, device=dev) if hist_len else None
-        self.K1.zero_(); self.cs.zero_()
-        b = _lib.GymBatch()
-        b.B, b.Bp, b.N, b.hist_len = self.B, self.Bp, self.N, self.hist_len
+
+    def _set_u0_flag(self, u0_zero):
         # tau1 is unactuated (dynamics.py:205); with u_ref[:,0] == 0 its controls stay exactly 0 and the
         # kernels skip their planes (GYM_FLAG_U0_ZERO) -- bit-identical results, 24 B/stage less traffic
         ref_u0_zero = bool((self.u_ref[..., 0] == 0).all().item())
@@ -349,6 +154,15 @@ class BatchedNewtonSolver:
             raise ValueError("u0_zero=True requires u_ref[:, 0] == 0")
         self.u0_zero = ref_u0_zero if u0_zero is None else bool(u0_zero)
         self._u0_cleared = False   # the flag is off for one warm-started solve whose u_init has tau1 != 0 (init)
+
+    def _choose_schedule(self, pipeline, persistent, schedule_lanes, checkpoint, chunk, reorder, split_waves):
+        """serial / pipelined / persistent (``schedule``), and how each runs."""
+        dev = self.eng.device
+        # the automatic schedule choice is made on ``schedule_lanes`` (default: this batch).  Sharded solves pass
+        # the largest shard of the global batch, so that every rank picks the same schedule: the schedules
+        # synchronise (all-reduce) at different points, and mixed choices would pair up the wrong collectives.
+        sched_B = self.B_sched = int(schedule_lanes) if schedule_lanes is not None else self.B
+        self.pipeline = (sched_B >= self.pipeline_min_lanes(dev)) if pipeline is None else bool(pipeline)
         # state checkpointing (GYM_FLAG_X_CKPT, opt-in): trials store x at every CKPT_INTERVAL-th knot only
         # and the sweep re-integrates the rest -- bit-identical results, 48 B/stage less traffic, but +0.75 RK4
         # per sweep stage: on MI355X the solver is as VALU- as HBM-limited and this measured 13% slower
@@ -365,27 +179,11 @@ class BatchedNewtonSolver:
         self.chunk = int(chunk)
         # solve() works on the lanes in the Morton order of their initial states (see morton_order)
         self.reorder = bool(reorder)
-        self.lane_order = None
         # persistent schedule on two wavefronts per 64 lanes (k_nt_run2: a helper wavefront takes the Jacobians,
         # the cost and the stores off the lanes' dependency chains; same bits) unless split_waves=False
         self.split_waves = bool(split_waves)
-        b.flags = ((_lib.FLAG_U0_ZERO if self.u0_zero else 0) | (_lib.FLAG_X_CKPT if self.checkpoint else 0) |
-                   (0 if self.split_waves else _lib.FLAG_RUN_SINGLE) | (_lib.FLAG_REF_LANE if self.ref_lane else 0))
-        for name in ("cost", "dJ", "smax", "gamma", "status", "n_iter", "res_buf", "n_roll",
-                     "retry_list", "counters", "cand_ok", "partials", "stats"):
-            setattr(b, name, getattr(self, name).data_ptr())
-        if self.ref_lane:
-            b.x_ref, b.u_ref = self.xr_buf.data_ptr(), self.ur_buf.data_ptr()
-        else:
-            b.x_ref, b.u_ref = self.x_ref.data_ptr(), self.u_ref.data_ptr()
-        b.hist_cost = _lib.ptr(self.hist_cost)
-        b.hist_smax = _lib.ptr(self.hist_smax)
-        self.batch = b
-        self._set_streams(st)
-        self.k = 0
-        self.timeline = None     # diagnostics: a list records (iterations, active lanes, host time) per sync
-        self.timing = None
-        self.launches = {"phase": 0, "run": 0, "tail": 0, "iteration": 0}   # launches since reset_timing()
+
+    def _set_capture(self, capture_lanes, capture_every, capture_sigma):
         # selected-lane trajectory capture (the reference's history['x_trajs'], trajectory_generation.py:322-327,
         # 387-388): after every iteration the captured lanes' current iterates are gathered on the device; the
         # persistent schedule then runs one iteration per launch.  Not combined with checkpointing (the state
@@ -400,6 +198,79 @@ class BatchedNewtonSolver:
         # sigma of the captured lanes at these iterations (the reference's report plots iterations 0, 1, 2 and the
         # last, trajectory_generation.py:341, 476-480; the last one is the solve's own sigma output)
         self.capture_sigma = tuple(sorted({int(i) for i in (capture_sigma or ())}))
+        self._cap_pos, self._cap_log, self._sig_log = None, [], []
+
+    def _alloc_streams(self, arena, placement_trials, auto_schedule):
+        """The six stream buffers [x0, x1, u0, u1, K1, cs]: the PlacementPool's set of this shape, carved from one
+        arena, or plain allocations.  Returns them and the number of placement trials."""
+        dev = self.eng.device
+        Bp, N, T = self.Bp, self.N, self.T
+        shapes = [(N, 2, Bp, 2), (N, 2, Bp, 2), (T, 2, Bp, 1), (T, 2, Bp, 1), (T, 2, Bp, 2), (T, 2, Bp, 1)]
+        self._stream_shapes = shapes
+        # placement selection: default for the automatic schedule's pipelined solvers (the only schedule whose
+        # throughput is the HBM streams'); a set chosen by an earlier solver of this shape in this process is reused
+        # from the PlacementPool without a probe
+        if placement_trials is None:
+            placement_trials = (self.PLACEMENT_TRIALS
+                                if auto_schedule and self.pipeline and not arena and not self.checkpoint else 1)
+        placement_trials = int(placement_trials)
+        self.placement = self._pl = None
+        self._pool_key = (torch.device(dev).index, tuple(shapes))
+        pooled = PlacementPool.take(self._pool_key) if placement_trials > 1 and not arena else None
+        if pooled is not None:
+            st, rec = pooled
+            self.placement = dict(rec, reused=True)
+        elif arena:
+            # the six streams carved from one allocation, each 2 MiB aligned, in this order (arena: True = a torch
+            # allocation, or a callable n -> fp64 device tensor of n elements that provides it)
+            al = (2 << 20) // 8
+            offs, n = [], 0
+            for sh in shapes:
+                offs.append(n)
+                n += -(-int(np.prod(sh)) // al) * al
+            self._arena = arena(n) if callable(arena) else torch.empty(n, dtype=F64, device=dev)
+            st = [self._arena[o:o + int(np.prod(sh))].view(sh) for o, sh in zip(offs, shapes)]
+        else:
+            st = [torch.empty(sh, dtype=F64, device=dev) for sh in shapes]
+        return st, placement_trials
+
+    def _alloc_lane_buffers(self, max_ls, hist_len):
+        dev = self.eng.device
+        e = lambda *s, dt=F64: torch.empty(s, dtype=dt, device=dev)  # noqa: E731
+        Bp, i32 = self.Bp, torch.int32
+        self.cost, self.dJ, self.smax, self.gamma = e(Bp), e(Bp), e(Bp), e(Bp)
+        self.status, self.n_iter, self.res_buf, self.n_roll = (e(Bp, dt=i32) for _ in range(4))
+        self.retry_list = e(Bp, dt=i32)
+        self.counters = torch.zeros(4, dtype=i32, device=dev)
+        self.cand_ok = torch.zeros((max(int(max_ls), 1), Bp), dtype=torch.uint8, device=dev)
+        self.partials = e(256 * 8)
+        self.stats = torch.zeros(24, dtype=F64, device=dev)     # [0,8) totals, [8,16) / [16,24) halves
+        self.hist_len = int(hist_len)
+        self.hist_cost = torch.full((hist_len, Bp), float("nan"), dtype=F64, device=dev) if hist_len else None
+        self.hist_smax = torch.full((hist_len, Bp), float("nan"), dtype=F64, device=dev) if hist_len else None
+
+    def _fill_batch(self):
+        """The gym_batch the launches take: sizes, flags and every buffer but the streams (_set_streams)."""
+        b = _lib.GymBatch()
+        b.B, b.Bp, b.N, b.hist_len = self.B, self.Bp, self.N, self.hist_len
+        b.flags = ((_lib.FLAG_U0_ZERO if self.u0_zero else 0) | (_lib.FLAG_X_CKPT if self.checkpoint else 0) |
+                   (0 if self.split_waves else _lib.FLAG_RUN_SINGLE) | (_lib.FLAG_REF_LANE if self.ref_lane else 0))
+        for name in ("cost", "dJ", "smax", "gamma", "status", "n_iter", "res_buf", "n_roll",
+                     "retry_list", "counters", "cand_ok", "partials", "stats"):
+            setattr(b, name, getattr(self, name).data_ptr())
+        if self.ref_lane:
+            b.x_ref, b.u_ref = self.xr_buf.data_ptr(), self.ur_buf.data_ptr()
+        else:
+            b.x_ref, b.u_ref = self.x_ref.data_ptr(), self.u_ref.data_ptr()
+        b.hist_cost = _lib.ptr(self.hist_cost)
+        b.hist_smax = _lib.ptr(self.hist_smax)
+        self.batch = b
+
+    def _set_eligibility(self, auto_schedule, tail_lanes, tail_chunk, compact, world_size, cand_slots):
+        """Which of the straggler tail, lane compaction and the candidate scratch this solver uses."""
+        max_ls = int(self.armijo.max_ls)
+        lockstep = not self.persistent and not self.checkpoint   # serial / pipelined with the full state store ...
+        whole = lockstep and self.capture_lanes is None          # ... and whole-iteration launches (no capture)
         # straggler tail (serial / pipelined schedules; needs the full state store, whole-iteration launches: no
         # trajectory capture, at most 64 Armijo trials): switch once the global active count is <= tail_lanes.
         # Default: on with the automatic schedule choice, TAIL_LANES_PER_CU per CU of every rank (``world_size``:
@@ -410,33 +281,25 @@ class BatchedNewtonSolver:
         # otherwise enter the tail with up to world x its budget of lanes, one workgroup each
         self.tail_lanes_rank = None
         if tail_lanes is None:
-            per_rank = (self.TAIL_LANES_PER_CU * torch.cuda.get_device_properties(dev).multi_processor_count
-                        if auto_schedule else 0)
+            n_cu = torch.cuda.get_device_properties(self.eng.device).multi_processor_count
+            per_rank = self.TAIL_LANES_PER_CU * n_cu if auto_schedule else 0
             tail_lanes = per_rank * max(int(world_size), 1)
             self.tail_lanes_rank = per_rank or None
         # the tail kernel's limits: at most 64 trials, horizons up to its LDS staging, and that LDS within the
         # device's opt-in limit (checked here, so a device with less LDS turns the tail off instead of failing mid-solve)
         need, lds, lds_max = C.c_int64(), C.c_int64(), C.c_int64()
-        tail_ok = (not self.persistent and not self.checkpoint and self.capture_lanes is None and
-                   engine.lib.gym_newton_tail_scratch(self.N, 1, int(max_ls), C.byref(need)) == 0 and
-                   engine.lib.gym_newton_tail_lds(self.N, C.byref(lds), C.byref(lds_max)) == 0 and
+        fits = lambda name, *a: self._launch(name, *a, check=False, **_SIZES) == 0  # noqa: E731
+        tail_ok = (whole and fits("gym_newton_tail_scratch", self.N, 1, max_ls, C.byref(need)) and
+                   fits("gym_newton_tail_lds", self.N, C.byref(lds), C.byref(lds_max)) and
                    lds.value <= lds_max.value)
         self.tail_lanes = int(tail_lanes) if tail_ok else 0
         self.tail_chunk = max(int(tail_chunk), 1)
+        self._tail_scratch = None
         # lane compaction (serial / pipelined schedules, solve(); see maybe_compact): default on with the automatic
         # schedule choice.  "force" compacts at every host synchronisation (tests)
         if compact is None:
             compact = auto_schedule
-        self.compact_mode = ("force" if compact == "force" else bool(compact)) if (
-            not self.persistent and not self.checkpoint and self.capture_lanes is None) else False
-        self.compactions = 0
-        self._compact_prev = None
-        self.lane_order_live = False   # True inside solve(), whose results follow lane_order back
-        self._serial_now = False
-        self._run_now = False
-        self.serial_switch_at = None   # the iteration the low-occupancy switch happened at
-        self._its_switch, self._its_tail_start = 0, None
-        self._tail_scratch = None
+        self.compact_mode = ("force" if compact == "force" else bool(compact)) if whole else False
         # candidate scratch (gym_batch.cand_scratch, ABI 13): the post-trial Armijo candidates of the serial /
         # pipelined schedules and the low-occupancy regime record their trajectories, and the accepted one is copied
         # instead of re-run (a T-step chain per backtracking iteration).  Slots for min(lanes x (max_ls - 1),
@@ -446,22 +309,44 @@ class BatchedNewtonSolver:
         # rejecting trial 1, on entering the low-occupancy regime, or for the tail; a solve in which no lane
         # backtracks (the headline workload) never holds it.  Until then the accepted candidates are re-run (the
         # same bits).
-        if cand_slots is None:
-            cand_slots = self.CAND_SLOTS
-        slots = min(self.Bp * max(int(max_ls) - 1, 0), int(cand_slots))
-        slots = slots // 64 * 64
+        cand_slots = int(self.CAND_SLOTS if cand_slots is None else cand_slots)
+        slots = min(self.Bp * max(max_ls - 1, 0), cand_slots) // 64 * 64
         self._cand_scratch = None
-        ok = slots > 0 and not self.persistent and not self.checkpoint and self.split_waves
-        self.cand_slots = slots if ok else 0
+        self.cand_slots = slots if slots > 0 and lockstep and self.split_waves else 0
+
+    def _reset_solve_counters(self):
+        """What solve() counts and reports per call (SolveResult's tail / compaction / low-occupancy fields)."""
         self.tail_lane_its = 0
         self.tail_from, self.tail_iters = None, 0
-        self._cap_pos = None
-        self._cap_log = []
-        self._sig_log = []
-        if self.placement is not None:            # a pooled set: back to the pool when this solver goes
-            self._lease_placement()
-        elif int(placement_trials) > 1 and self.pipeline and not self.persistent:
-            self._arm_placement(int(placement_trials))
+        self.compactions = 0
+        self._compact_prev = None
+        self.serial_switch_at = None   # the iteration the low-occupancy switch happened at
+        self._its_switch, self._its_tail_start = 0, None
+
+    # --- launches and streams --------------------------------------------------------------
+    def _launch(self, name, *args, pre=(), model=True, weights=None, armijo=False, batch=True, stream=True,
+                check=True):
+        """Call the library's ``name`` as (model, weights[, armijo], *pre, batch, *args, stream) -- the keywords drop
+        or add a part (``weights`` follows ``model`` unless given) -- and raise on a non-zero return code unless
+        ``check`` is off.  Returns the code."""
+        eng = self.eng
+        a = []
+        if model:
+            a.append(C.byref(eng.model))
+        if model if weights is None else weights:
+            a.append(C.byref(eng._w))
+        if armijo:
+            a.append(C.byref(self.armijo))
+        a += pre
+        if batch:
+            a.append(C.byref(self.batch))
+        a += args
+        if stream:
+            a.append(eng.stream)
+        rc = getattr(eng.lib, name)(*a)
+        if check:
+            _lib.check(rc, name)
+        return rc
 
     def _set_streams(self, st, zero: bool = True):
         """Use the stream set st = [x0, x1, u0, u1, K1, cs]; ``zero``: K1 and cs zeroed, as at construction (False: a
@@ -472,11 +357,10 @@ class BatchedNewtonSolver:
         self.cs = st[5]                                # planes: cg = (u1 - K1 x) + gamma0 sigma1, sigma1
         if zero:
             self.K1.zero_(); self.cs.zero_()
-        b = getattr(self, "batch", None)
-        if b is not None:
-            b.x[0], b.x[1] = self.x[0].data_ptr(), self.x[1].data_ptr()
-            b.u[0], b.u[1] = self.u[0].data_ptr(), self.u[1].data_ptr()
-            b.K1, b.cs = self.K1.data_ptr(), self.cs.data_ptr()
+        b = self.batch
+        b.x[0], b.x[1] = self.x[0].data_ptr(), self.x[1].data_ptr()
+        b.u[0], b.u[1] = self.u[0].data_ptr(), self.u[1].data_ptr()
+        b.K1, b.cs = self.K1.data_ptr(), self.cs.data_ptr()
 
     def _streams(self) -> list:
         return [*self.x, *self.u, self.K1, self.cs]
@@ -490,140 +374,29 @@ class BatchedNewtonSolver:
             dst.copy_(src)
         self._set_streams(st, zero=False)
 
-    # --- placement selection ---------------------------------------------------------------
-    # Why placements differ (profiles/r06/README.md): on a slow set the same fabric requests come back later (+13..24%
-    # read latency, ~2x the L2's DRAM-credit and write stalls; no more translation misses, no channel imbalance), and
-    # the slowness follows how the streams the same waves touch in lock step lie relative to each other in physical
-    # memory; no allocation rule reachable from user space fixes it (contiguous VRAM at 200 layouts, record layouts),
-    # so the solver measures: candidates ranked by the placement probe, the best raced in the first solve, the winner
-    # pooled for the process's later solvers of the same shape.
+    # --- placement selection (placement.py) ------------------------------------------------
     def _arm_placement(self, trials: int, candidates: int | None = None):
-        """Allocate up to ``candidates`` - 1 further stream sets (while the free memory allows, beside the lane-major
-        results a solve allocates), rank all of them with the placement probe and keep the ``trials`` best for the
-        online selection of the next solve (_placement_tick); the others go back to the device."""
-        dev = self.eng.device
-        candidates = max(int(candidates or self.PLACEMENT_CANDIDATES), int(trials))
-        set_bytes = 8 * sum(int(np.prod(sh)) for sh in self._stream_shapes)
+        """Set up the online selection among stream sets for the next solve (PlacementSelection.arm)."""
         B, N, T = self.B, self.N, self.T
         results_bytes = 8 * B * (4 * N + 2 * T + 8 * T + 2 * T)      # finalize's x, u, K, sigma
-        free, total = torch.cuda.mem_get_info(dev)
-        # beside the results a solve allocates, and at most PLACEMENT_MEM_SHARE of the device for the extra sets (so
-        # that processes sharing a GPU leave each other room); an allocation that fails (another process was faster)
-        # just ends the candidate list
-        room = min(free - results_bytes - (4 << 30), self.PLACEMENT_MEM_SHARE * total)
-        k = min(candidates, 1 + max(0, int(room // max(set_bytes, 1))))
-        if k < 2:
-            return
-        t0 = time.perf_counter()
-        sets = [self._streams()]
-        try:
-            for _ in range(k - 1):
-                sets.append([torch.empty(sh, dtype=F64, device=dev) for sh in self._stream_shapes])
-        except torch.cuda.OutOfMemoryError:
-            torch.cuda.empty_cache()
-        k = len(sets)
-        if k < 2:
-            return
-        screen = None
-        if k > trials and self.Bp % 128 == 0:
-            # rank the candidates by the placement probe (two rounds, each set's faster launch), keep the best
-            ms = [float("inf")] * k
-            for r in range(2):
-                for i, st in enumerate(sets):
-                    self._set_streams(st, zero=False)
-                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                    ev[0].record()
-                    _lib.check(self.eng.lib.gym_placement_probe(C.byref(self.batch), r & 1, self.eng.stream),
-                               "gym_placement_probe")
-                    ev[1].record()
-                    ev[1].synchronize()
-                    ms[i] = min(ms[i], ev[0].elapsed_time(ev[1]))
-            keep = sorted(range(k), key=lambda i: ms[i])[:trials]
-            screen = {"candidates": k, "probe_ms": ms, "kept": keep}
-            sets = [sets[i] for i in keep]
-            torch.cuda.empty_cache()                # the screened-out sets go back to the device
-        self._set_streams(sets[0])                  # K1, cs zeroed (the probe left garbage), as at construction
-        if len(sets) < 2:
-            return
-        self._pl = {"sets": sets, "cur": 0, "attempts": 0, "alloc_s": time.perf_counter() - t0, "screen": screen}
-        self.placement = {"trials": len(sets), "state": "pending", "alloc_s": self._pl["alloc_s"], "screen": screen}
+        # the probe kernel runs workgroups of two wavefronts: other batches race their sets unranked
+        probe = (lambda cb: self._launch("gym_placement_probe", cb, model=False)) if self.Bp % 128 == 0 else None
+        self._pl = placement.PlacementSelection.arm(
+            self, self._pool_key, trials, candidates or self.PLACEMENT_CANDIDATES, self.PLACEMENT_BLOCK,
+            self.PLACEMENT_MEM_SHARE, results_bytes, probe)
+        if self._pl is not None:
+            self.placement = self._pl.record
 
-    def _placement_start(self):
-        """(init) A new solve: the selection schedule restarts from the set in use, in the order c, the others, then
-        the reverse (each set runs two blocks placed symmetrically, so a drift of the iterations' cost over the probe
-        cancels out of the comparison)."""
-        pl = self._pl
-        pl["attempts"] += 1
-        if pl["attempts"] > 2:                     # two solves ended before the probe did: keep the set in use
-            self._placement_finish(abandon=True)
-            return
-        k = len(pl["sets"])
-        seq = [pl["cur"]] + [i for i in range(k) if i != pl["cur"]]
-        pl.update(order=seq + seq[::-1], blocks=[], open=None, copies=0)
-
-    def _placement_tick(self):
-        """(iteration, before its launches) At the block boundaries of the schedule: close the running block with an
-        event, move the state to the next block's set, open the next block.  Only on the pipelined schedule while it
-        runs its phases (the low-occupancy regime and the tail end the probe for this solve)."""
-        pl = self._pl
-        if self._serial_now or self._run_now or "order" not in pl:
-            return
-        k, n = self.k, self.PLACEMENT_BLOCK
-        if k % n:
-            return
-        if pl["open"] is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            pl["blocks"].append((*pl["open"], ev))
-            pl["open"] = None
-        i = k // n
-        if i >= len(pl["order"]):
-            self._placement_finish()
-            return
-        target = pl["order"][i]
-        if target != pl["cur"]:
-            self._move_streams(pl["sets"][target])
-            pl["cur"] = target
-            pl["copies"] += 1
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        pl["open"] = (target, ev)
-
-    def _placement_finish(self, abandon: bool = False):
-        """Keep the fastest set (by the mean of its blocks' ms per iteration), release the others, and lease the kept
-        one to this solver (back to the PlacementPool when the solver goes)."""
-        pl, n = self._pl, self.PLACEMENT_BLOCK
-        per = {}
-        for s, e0, e1 in pl.get("blocks", []):
-            e1.synchronize()
-            per.setdefault(s, []).append(e0.elapsed_time(e1) / n)
-        best = pl["cur"]
-        if not abandon and per:
-            best = min(per, key=lambda s: sum(per[s]) / len(per[s]))
-            if best != pl["cur"]:
-                self._move_streams(pl["sets"][best])
-                pl["copies"] += 1
-        self.placement = {"trials": len(pl["sets"]), "state": "abandoned" if abandon else "chosen", "chosen": best,
-                          "ms_per_iteration": {int(s): v for s, v in sorted(per.items())},
-                          "probe_iterations": n * len(pl.get("blocks", [])), "copies": pl.get("copies", 0),
-                          "alloc_s": pl["alloc_s"], "at_iteration": int(self.k), "screen": pl.get("screen")}
-        self._pl = None
-        pl.clear()
-        torch.cuda.empty_cache()                    # the unused sets go back to the device, not the process's cache
-        self._lease_placement()
-
-    def _lease_placement(self):
-        st, rec = self._streams(), {k: v for k, v in self.placement.items() if k != "reused"}
-        f = weakref.finalize(self, PlacementPool.put, self._pool_key, st, rec)
-        f.atexit = False
+    def _end_placement(self):
+        """The selection is over (its start() or tick() said so): its record stays, the object goes."""
+        self.placement, self._pl = self._pl.record, None
 
     def ensure_cand_scratch(self) -> bool:
         """Allocate the candidate scratch (cand_slots slots, ~24 KiB each at T = 500) if this solver uses one and has
         not yet; stream-ordered, so the next launch may use it.  Returns whether it is in place."""
         if self._cand_scratch is None and self.cand_slots > 0:
             need = C.c_int64()
-            _lib.check(self.eng.lib.gym_newton_cand_scratch(self.N, self.cand_slots, C.byref(need)),
-                       "gym_newton_cand_scratch")
+            self._launch("gym_newton_cand_scratch", self.N, self.cand_slots, C.byref(need), **_SIZES)
             self._cand_scratch = torch.empty(int(need.value), dtype=F64, device=self.eng.device)
             self.batch.cand_scratch, self.batch.cand_slots = self._cand_scratch.data_ptr(), self.cand_slots
         return self._cand_scratch is not None
@@ -639,7 +412,7 @@ class BatchedNewtonSolver:
         if self.schedule != "pipelined":
             return None
         lo = C.c_int32()
-        _lib.check(self.eng.lib.gym_newton_phase_kind(C.byref(self.batch), C.byref(lo)), "gym_newton_phase_kind")
+        self._launch("gym_newton_phase_kind", C.byref(lo), model=False, stream=False)
         return "two-wavefront" if lo.value else "four-wavefront"
 
     # --- optional per-kernel HIP-event timing (on the solver's stream) ---------------------
@@ -735,11 +508,10 @@ class BatchedNewtonSolver:
             self.xr_buf[:self.B] = self._xr_in if _ref_perm is None else self._xr_in[_ref_perm]
             self.ur_buf[:self.B] = self._ur_in if _ref_perm is None else self._ur_in[_ref_perm]
         self._x0 = x0
-        if self._pl is not None:
-            self._placement_start()
+        if self._pl is not None and self._pl.start(self):
+            self._end_placement()
         if u_init is None:
-            _lib.check(self.eng.lib.gym_newton_init(C.byref(self.eng.model), C.byref(self.eng._w), x0.data_ptr(),
-                                                    C.byref(self.batch), self.eng.stream), "gym_newton_init")
+            self._launch("gym_newton_init", pre=(x0.data_ptr(),))
         else:
             if self.u0_zero and bool((u_init[..., 0] != 0).any().item()):
                 self._set_u0_zero(False)
@@ -748,10 +520,7 @@ class BatchedNewtonSolver:
             # finalize's use of the field)
             self.batch.lane_map = None if _lane_map is None else _lane_map.data_ptr()
             try:
-                _lib.check(self.eng.lib.gym_newton_init_warm(C.byref(self.eng.model), C.byref(self.eng._w),
-                                                             x0.data_ptr(), u_init.data_ptr(), _lib.ptr(status_init),
-                                                             C.byref(self.batch), self.eng.stream),
-                           "gym_newton_init_warm")
+                self._launch("gym_newton_init_warm", pre=(x0.data_ptr(), u_init.data_ptr(), _lib.ptr(status_init)))
             finally:
                 self.batch.lane_map = None
         self.k = 0
@@ -765,9 +534,7 @@ class BatchedNewtonSolver:
 
     def _run(self, k0: int, k1: int):
         self.launches["run"] += 1
-        _lib.check(self.eng.lib.gym_newton_run(C.byref(self.eng.model), C.byref(self.eng._w), C.byref(self.armijo),
-                                               C.byref(self.batch), int(k0), int(k1), self.eng.stream),
-                   "gym_newton_run")
+        self._launch("gym_newton_run", int(k0), int(k1), armijo=True)
 
     def tail_run(self, k0: int, k1: int) -> torch.Tensor:
         """Iterations k0 .. k1-1 of every lane still active, on the straggler-tail kernel (gym_newton_tail: one
@@ -777,8 +544,7 @@ class BatchedNewtonSolver:
         lanes = (self.status[:self.B] == _lib.ACTIVE).nonzero().flatten().to(torch.int32)
         n = int(lanes.numel())
         need = C.c_int64()
-        _lib.check(self.eng.lib.gym_newton_tail_scratch(self.N, n, int(self.armijo.max_ls), C.byref(need)),
-                   "gym_newton_tail_scratch")
+        self._launch("gym_newton_tail_scratch", self.N, n, int(self.armijo.max_ls), C.byref(need), **_SIZES)
         self.ensure_cand_scratch()
         if self._cand_scratch is not None and self._cand_scratch.numel() >= need.value:
             sc = self._cand_scratch          # the candidate scratch (the tail and the post-trial kernels never overlap)
@@ -788,23 +554,19 @@ class BatchedNewtonSolver:
                 self._tail_scratch = torch.empty(int(need.value), dtype=F64, device=self.eng.device)
             sc = self._tail_scratch
         self.launches["tail"] += 1
-        _lib.check(self.eng.lib.gym_newton_tail(C.byref(self.eng.model), C.byref(self.eng._w), C.byref(self.armijo),
-                                                C.byref(self.batch), lanes.data_ptr() if n else None, n,
-                                                sc.data_ptr(), int(sc.numel()), int(k0), int(k1), self.eng.stream),
-                   "gym_newton_tail")
+        self._launch("gym_newton_tail", lanes.data_ptr() if n else None, n, sc.data_ptr(), int(sc.numel()),
+                     int(k0), int(k1), armijo=True)
         self.k = int(k1)
         return self.stats[:8]
 
     def _phase(self, p: int, do_backward: bool):
         self.launches["phase"] += 1
-        _lib.check(self.eng.lib.gym_newton_phase(C.byref(self.eng.model), C.byref(self.eng._w), C.byref(self.armijo),
-                                                 C.byref(self.batch), p, int(do_backward), self.eng.stream),
-                   "gym_newton_phase")
+        self._launch("gym_newton_phase", p, int(do_backward), armijo=True)
 
     def iteration(self) -> torch.Tensor:
         """Enqueue outer iteration k for every active lane; returns the 8 total statistics (device)."""
-        if self._pl is not None:
-            self._placement_tick()
+        if self._pl is not None and self._pl.tick(self):
+            self._end_placement()
         k = self.k
         if self.persistent or self._run_now:
             self._run(k, k + 1)
@@ -814,9 +576,7 @@ class BatchedNewtonSolver:
             self._phase(2 * k + 2, more)         # sweep H0 (iteration k+1) beside trial H1 (iteration k)
         else:
             self.launches["iteration"] += 1
-            _lib.check(self.eng.lib.gym_newton_iteration(C.byref(self.eng.model), C.byref(self.eng._w),
-                                                         C.byref(self.armijo), C.byref(self.batch), k,
-                                                         self.eng.stream), "gym_newton_iteration")
+            self._launch("gym_newton_iteration", k, armijo=True)
         self.k += 1
         self._capture()
         return self.stats[:8]
@@ -890,14 +650,8 @@ class BatchedNewtonSolver:
 
     def finalize(self):
         B, N, T, dev = self.B, self.N, self.T, self.eng.device
-        x = torch.empty((B, N, 4), dtype=F64, device=dev)
-        u = torch.empty((B, T, 2), dtype=F64, device=dev)
-        K = torch.empty((B, T, 2, 4), dtype=F64, device=dev)
-        s = torch.empty((B, T, 2), dtype=F64, device=dev)
-        _lib.check(self.eng.lib.gym_newton_finalize(C.byref(self.eng.model), C.byref(self.eng._w), C.byref(self.batch),
-                                                    self.k, x.data_ptr(),
-                                                    u.data_ptr(), K.data_ptr(), s.data_ptr(), self.eng.stream),
-                   "gym_newton_finalize")
+        x, u, K, s = (torch.empty((B, *sh), dtype=F64, device=dev) for sh in ((N, 4), (T, 2), (T, 2, 4), (T, 2)))
+        self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), s.data_ptr())
         return x, u, K, s
 
     def states(self, buf: int) -> torch.Tensor:
@@ -905,8 +659,7 @@ class BatchedNewtonSolver:
         This is the solver's live stream buffer, not a copy: the next iteration overwrites it, and once this solver
         is gone the PlacementPool may hand the same memory to the next solver of the same shape.  Clone what must
         outlive either (unpack() already copies)."""
-        _lib.check(self.eng.lib.gym_newton_fill_states(C.byref(self.eng.model), C.byref(self.batch), int(buf),
-                                                       self.eng.stream), "gym_newton_fill_states")
+        self._launch("gym_newton_fill_states", int(buf), weights=False)
         return self.x[buf]
 
     def gamma_sweep(self, gammas) -> torch.Tensor:
@@ -919,9 +672,7 @@ class BatchedNewtonSolver:
         if G < 1:
             raise ValueError("gamma_sweep needs at least one step size")
         J = torch.empty((G, self.Bp), dtype=F64, device=self.eng.device)
-        _lib.check(self.eng.lib.gym_newton_gamma_sweep(C.byref(self.eng.model), C.byref(self.eng._w),
-                                                       C.byref(self.armijo), C.byref(self.batch), self.k, g.data_ptr(), G, J.data_ptr(),
-                                                       self.eng.stream), "gym_newton_gamma_sweep")
+        self._launch("gym_newton_gamma_sweep", self.k, g.data_ptr(), G, J.data_ptr(), armijo=True)
         return J[:, :self.B].t()
 
     def gains(self) -> torch.Tensor:
@@ -957,9 +708,7 @@ class BatchedNewtonSolver:
             s[..., 0] = -0.0
             return s
         s = torch.empty((self.B, self.T, 2), dtype=F64, device=self.eng.device)
-        _lib.check(self.eng.lib.gym_newton_sigma(C.byref(self.eng.model), C.byref(self.eng._w), C.byref(self.batch),
-                                                 s.data_ptr(),
-                                                 self.eng.stream), "gym_newton_sigma")
+        self._launch("gym_newton_sigma", s.data_ptr())
         return s
 
     # --- lane compaction ------------------------------------------------------------------
@@ -1025,8 +774,7 @@ class BatchedNewtonSolver:
             self._enter_low_occupancy()
         if pipelined:
             Bh = C.c_int64()
-            _lib.check(self.eng.lib.gym_newton_pipeline_split(C.byref(self.batch), C.byref(Bh)),
-                       "gym_newton_pipeline_split")
+            self._launch("gym_newton_pipeline_split", C.byref(Bh), model=False, stream=False)
             ranges = [(0, int(Bh.value)), (int(Bh.value), B)]
         else:
             ranges = [(0, B)]
@@ -1094,13 +842,7 @@ class BatchedNewtonSolver:
             inv = torch.empty_like(perm)
             inv[perm] = torch.arange(self.B, device=perm.device)
             self._capture_start(inv[torch.as_tensor(self.capture_lanes, device=perm.device)].tolist())
-        self.tail_lane_its = 0
-        self.tail_from, self.tail_iters = None, 0
-        self.compactions = 0
-        self._compact_prev = None
-        self.serial_switch_at = None
-        self._its_switch = 0
-        self._its_tail_start = None
+        self._reset_solve_counters()
         if self.persistent:
             log = run_loop(self, int(max_iters), reduce_stats, log_every, keep_stats)
         else:
@@ -1132,22 +874,18 @@ class BatchedNewtonSolver:
         secs = time.perf_counter() - t0
         # persistent: the lanes' own iteration counts (no lock-step outer loop); otherwise the loop's count
         iters = int(n_iter.max().item()) if self.persistent else self.k
-        res["x_trajs"] = self.captured_trajectories() if self.capture_lanes is not None else None
-        res["cost0"] = self.captured_initial_costs() if self.capture_lanes is not None else None
-        res["sigmas"] = self.captured_sigmas() if self.capture_lanes is not None else None
-        res["schedule"] = self.schedule
-        res["tail_lane_iterations"] = int(self.tail_lane_its)
-        res["tail_from_iteration"] = self.tail_from
-        res["tail_iterations"] = int(self.tail_iters)
-        res["compactions"] = int(self.compactions)
+        if self.capture_lanes is not None:
+            res.update(x_trajs=self.captured_trajectories(), cost0=self.captured_initial_costs(),
+                       sigmas=self.captured_sigmas())
         lowocc = 0
         if self.serial_switch_at is not None:   # up to the tail switch, or the end of the solve
             end = self._its_tail_start if self._its_tail_start is not None else int(n_iter.sum().item())
             lowocc = end - self._its_switch
-        res["lowocc_lane_iterations"] = int(lowocc)
         return SolveResult(x=x, u=u, K=K, sigma=s, n_iter=n_iter, iterations=iters,
-                           lane_iterations=int(n_iter.sum().item()), seconds=secs, stats_log=log, **res)
-
+                           lane_iterations=int(n_iter.sum().item()), seconds=secs, stats_log=log,
+                           schedule=self.schedule, tail_lane_iterations=int(self.tail_lane_its),
+                           tail_from_iteration=self.tail_from, tail_iterations=int(self.tail_iters),
+                           compactions=int(self.compactions), lowocc_lane_iterations=int(lowocc), **res)
 
     def resume(self, ckpt: Checkpoint, max_iters: int, **solve_kw) -> SolveResult:
         """Continue a checkpoint (load_checkpoint) for up to ``max_iters`` further iterations:
@@ -1178,161 +916,6 @@ class BatchedNewtonSolver:
         r.n_iter = r.n_iter + c["n_iter"].to(r.n_iter.dtype)
         r.n_rollouts = r.n_rollouts + c["n_rollouts"].to(r.n_rollouts.dtype)
         return r
-
-
-def morton_order(x0: torch.Tensor, bits: int = 10) -> torch.Tensor:
-    """Lane permutation along a Z-order (Morton) curve over the initial states x0 (B,4).
-
-    A wavefront runs until the last of its 64 lanes has converged, so lanes that need different iteration
-    counts waste the slots of the early finishers (on the headline workload, lanes converge after 381-404
-    iterations: 97.8% of the slots do useful work in input order).  Neighbouring initial states converge in
-    similar counts; grouping them along a space-filling curve raises that to 99.7% (C oracle, 8,192 lanes).
-    Each coordinate is quantised to ``bits`` bits over the batch's range (non-finite values as 0) and the
-    bits are interleaved; ties keep the input order."""
-    x = torch.nan_to_num(x0, nan=0.0, posinf=0.0, neginf=0.0)
-    lo, hi = x.min(0).values, x.max(0).values
-    span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
-    q = ((x - lo) / span * (2 ** bits - 1)).clamp(0, 2 ** bits - 1).to(torch.int64)
-    key = torch.zeros(x.shape[0], dtype=torch.int64, device=x.device)
-    d = x.shape[1]
-    for b in range(bits):
-        for j in range(d):
-            key |= ((q[:, j] >> b) & 1) << (b * d + j)
-    return torch.argsort(key, stable=True)
-
-
-def run_loop(solver: BatchedNewtonSolver, max_iters: int, reduce_stats, log_every: int, keep_stats: bool):
-    """Persistent schedule: launches of ``chunk`` iterations (0: all of max_iters); after each one the
-    statistics are all-reduced across ranks (``reduce_stats``) and read, and the loop stops when no lane of any
-    rank is active."""
-    log = []
-    chunk = solver.chunk if solver.chunk > 0 else max(int(max_iters), 1)
-    # trajectory capture: one iteration per launch, but the statistics are still read (and all-reduced) at the
-    # same iterations as without capture, so ranks that capture and ranks that do not stay paired
-    step = 1 if solver._cap_pos is not None else chunk
-    k = 0
-    while k < max_iters:
-        k1 = min(int(max_iters), k + step)
-        solver._run(k, k1)
-        solver.k = k = k1
-        solver._capture()
-        if k % chunk and k < max_iters:
-            continue
-        st = solver.stats[:8]
-        if reduce_stats is not None:
-            st = reduce_stats(st)
-        host = st.cpu().numpy()
-        solver.collect_timing()
-        if keep_stats:
-            log.append(host.copy())
-        if log_every:
-            print(f"iter {k}: active={int(host[0])} sumJ={host[1]:.6e} ran={int(host[3])}", flush=True)
-        if host[0] == 0:
-            break
-    return log
-
-
-def newton_loop(stepper, max_iters: int, reduce_stats=None, sync_every: int = 1, log_every: int = 0,
-                keep_stats: bool = False) -> list:
-    """Outer Newton loop shared by every stepper (HIP solver; the test oracle stepper).
-
-    ``stepper.iteration()`` enqueues one iteration for all of its lanes and returns the 8-entry
-    statistics tensor (STAT_FIELDS).  Every ``sync_every`` iterations the statistics are
-    all-reduced across ranks (``reduce_stats``, SUM) and read on the host; the loop stops when no
-    lane of any rank is active.  Returns the list of host statistics if ``keep_stats``."""
-    log = []
-    tail = int(getattr(stepper, "tail_lanes", 0) or 0)
-    compact = getattr(stepper, "maybe_compact", None) if getattr(stepper, "lane_order_live", False) else None
-    for k in range(int(max_iters)):
-        st = stepper.iteration()
-        if (k + 1) % sync_every == 0 or k + 1 == max_iters:
-            local = st
-            if reduce_stats is not None:
-                st = reduce_stats(st)
-            host = st.cpu().numpy() if isinstance(st, torch.Tensor) else np.asarray(st)
-            collect = getattr(stepper, "collect_timing", None)
-            if collect is not None:
-                collect()
-            if keep_stats:
-                log.append(host.copy())
-            if getattr(stepper, "timeline", None) is not None:   # diagnostics: (iterations, active, host time)
-                stepper.timeline.append((k + 1, int(host[0]), time.perf_counter()))
-            if log_every and (k % log_every == 0):
-                print(f"iter {k}: active={int(host[0])} sumJ={host[1]:.6e} ran={int(host[3])} "
-                      f"retry={int(host[4])}", flush=True)
-            if host[0] == 0:
-                break
-            if host[4] > 0:   # lanes rejected trial 1: from now on the post-trial search records its candidates
-                ensure = getattr(stepper, "ensure_cand_scratch", None)
-                if ensure is not None:
-                    ensure()
-            # the straggler tail: decided on the (all-reduced) global active count, so every rank switches at the
-            # same iteration and pairs up the same collectives afterwards; with a per-rank budget (tail_lanes_rank)
-            # also on the largest rank's own count, all-reduced (MAX) by every rank at the same iteration (they all
-            # see the same global count)
-            if tail and host[0] <= tail and k + 1 < max_iters and _tail_rank_ok(stepper, host, local, reduce_stats):
-                log += tail_loop(stepper, k + 1, int(max_iters), reduce_stats, log_every, keep_stats)
-                break
-            if compact is not None and k + 1 < max_iters:   # rank-local: no collective depends on it
-                compact(int(local[0].item()) if reduce_stats is not None else int(host[0]))
-    return log
-
-
-def _tail_rank_ok(stepper, host, local, reduce_stats) -> bool:
-    """The per-rank part of the straggler-tail switch: the largest rank's active count within ``tail_lanes_rank``
-    (None: no per-rank budget).  Sharded, the maximum is one MAX all-reduce (``reduce_stats.max_of``) that every rank
-    issues at the same iteration; with a reducer that has no ``max_of`` the budget is not applied (a warning)."""
-    cap = getattr(stepper, "tail_lanes_rank", None)
-    if cap is None:
-        return True
-    if reduce_stats is None:
-        return host[0] <= cap
-    max_of = getattr(reduce_stats, "max_of", None)
-    if max_of is None:
-        # a caller-supplied reducer without a MAX: the per-rank budget cannot be checked without a collective the
-        # other ranks would not pair, so the global threshold alone decides (comparing the global count with the
-        # per-rank cap would delay the tail until the whole job fits one rank's budget)
-        if not getattr(stepper, "_warned_no_max_of", False):
-            import warnings
-            warnings.warn("reduce_stats has no max_of: the straggler tail's per-rank budget is not applied")
-            stepper._warned_no_max_of = True
-        return True
-    n = float(local[0].item()) if isinstance(local, torch.Tensor) else float(np.asarray(local)[0])
-    return max_of(n) <= cap
-
-
-def tail_loop(solver, k: int, max_iters: int, reduce_stats, log_every: int, keep_stats: bool) -> list:
-    """The rest of a serial / pipelined solve on the straggler-tail kernel, ``tail_chunk`` iterations per launch
-    (a lane stops inside a launch when it finishes; the launch ends with its last lane); the statistics are
-    all-reduced and read after each launch, and the loop stops when no lane of any rank is active."""
-    log = []
-    k_switch = k
-    its0 = int(solver.n_iter[:solver.B].sum().item())
-    solver._its_tail_start = its0
-    while k < max_iters:
-        k1 = min(max_iters, k + solver.tail_chunk)
-        st = solver.tail_run(k, k1)
-        k = k1
-        if reduce_stats is not None:
-            st = reduce_stats(st)
-        host = st.cpu().numpy()
-        solver.collect_timing()
-        if keep_stats:
-            log.append(host.copy())
-        if getattr(solver, "timeline", None) is not None:
-            solver.timeline.append((k, int(host[0]), time.perf_counter()))
-        if log_every:
-            print(f"tail iter {k}: active={int(host[0])} sumJ={host[1]:.6e}", flush=True)
-        if host[0] == 0:
-            break
-    solver.tail_lane_its = int(solver.n_iter[:solver.B].sum().item()) - its0
-    # a launch runs up to tail_chunk iterations but ends with its last lane: report the last iteration a lane ran,
-    # not the end of the chunk.  Sharded (reduce_stats): the chunk end, identical on every rank, as the lock-step loop
-    # reports its global count (a rank-local maximum would differ between ranks)
-    if reduce_stats is None and solver.B:
-        solver.k = max(k_switch, min(solver.k, int(solver.n_iter[:solver.B].max().item())))
-    solver.tail_from, solver.tail_iters = k_switch, solver.k - k_switch
-    return log
 
 
 def newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, gamma_0=1.0,
