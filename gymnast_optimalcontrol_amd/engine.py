@@ -4,8 +4,15 @@ Every method is a thin launcher over one C-ABI entry point of include/gymnast_ac
 arithmetic runs in the gfx950 kernels of csrc/: the Newton solver and its primitives in acrobot_kernels.hip
 (kernels in newton_*.hpp), the trackers in tracking_kernels.hip (kernels in tracking_dense.hpp, mpc_gains.hpp,
 track_rollout.hpp, mpc_box.hpp and the per-lane lqr_lanes.hpp, mpc_lanes.hpp, mpc_box_lanes.hpp).  Inputs are fp64
-tensors (any device / numpy are copied to the engine's HIP device); outputs stay on the device.  The trackers'
-argument checks are the module-level check_* functions at the end: they need no device and no engine.
+tensors (any device / numpy are copied to the engine's HIP device); outputs stay on the device.
+
+Each launch fact is stated once.  AcrobotEngine._call is the one path into the library: it turns structs, tensors
+and host arrays into what the ABI takes, appends the stream and checks the return code.  _buf allocates every
+buffer, _workspace hands over a caller's workspace or a fresh one, and one prelude per family (_trajectory, _gains,
+_stages) converts, checks and packs the shared arguments.  The ABI takes buffer sizes on trust (B, Bp, N and bare
+addresses), so the preludes compare every tensor with what the kernel reads and refuse a short one on the host,
+before any launch; spare trailing rows are never read and stay legal.  The argument rules are the module-level
+check_* functions at the end: they need no device and no engine.
 
 Lane-major shapes follow the reference stacked over lanes: x (B,N,4), u (B,T,2), K (B,T,2,4),
 sigma (B,T,2).  Internally trajectories live in the SoA "pairs" layout (see the header).
@@ -21,7 +28,7 @@ import torch
 from . import _lib
 from .params import PARAM_SETS, DT, Q_DIAG, R_DIAG, QT_DIAG
 
-F64 = torch.float64
+F64, I32, U8 = torch.float64, torch.int32, torch.uint8
 
 
 def padded(B: int) -> int:
@@ -80,13 +87,42 @@ class AcrobotEngine:
         self.dt = float(dt)
         self.model = _lib.GymModel()
         vec = np.array([p[k] for k in ("m1", "m2", "l1", "lc1", "l2", "lc2", "I1", "I2", "g", "f1", "f2")], float)
-        _lib.check(self.lib.gym_model_from_params(vec.ctypes.data, self.dt, C.byref(self.model)),
-                   "gym_model_from_params")
+        self._call("gym_model_from_params", vec, self.dt, self.model, stream=False)
         self.weights = weights or Weights()
         self._w = self.weights.c_struct()
         self.mpc_qt_cache = {}     # (Q, R) -> Q_T of per-lane MPC tracking; it depends on this engine's model and dt
 
     # -------------------------------------------------------------------------------- utils
+    def _call(self, name: str, *args, stream: bool = True):
+        """The one path into the library: call its entry point ``name`` and raise on a non-zero return code.  A
+        ctypes struct goes by reference, a tensor as its device address, a host array as its address; None, ints,
+        floats and ready-made byref out-parameters pass as they are; the engine's stream comes last unless
+        ``stream`` is off.  What the library would misread is a TypeError: a tensor that is not contiguous or not
+        on the engine's device, an array that is not C-contiguous float64 (an invariant of this file's own code,
+        not a check of the caller's arguments)."""
+        a = []
+        for v in args:
+            if isinstance(v, torch.Tensor):
+                dev = v.device
+                if not v.is_contiguous() or dev.type != self.device.type or self.device.index not in (None, dev.index):
+                    raise TypeError(f"{name}: tensor {tuple(v.shape)} on {dev} is not contiguous on {self.device}")
+                v = v.data_ptr()
+            elif isinstance(v, np.ndarray):
+                if v.dtype != np.float64 or not v.flags.c_contiguous:
+                    raise TypeError(f"{name}: host array {v.shape} {v.dtype} is not C-contiguous float64")
+                v = v.ctypes.data
+            elif isinstance(v, C.Structure):
+                v = C.byref(v)
+            a.append(v)
+        if stream:
+            a.append(self.stream)
+        _lib.check(getattr(self.lib, name)(*a), name)
+
+    def _buf(self, *shape, dtype=F64, zero: bool = False, want: bool = True):
+        """An uninitialised (``zero``: zero-filled) buffer on the engine's device; None for an optional output the
+        caller does not ``want``."""
+        return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device) if want else None
+
     def t(self, a, shape=None) -> torch.Tensor:
         """fp64 contiguous tensor on the engine device."""
         if isinstance(a, torch.Tensor):
@@ -110,19 +146,25 @@ class AcrobotEngine:
         W = 1 planes (controls, sigma).  The tensor shape only sizes the buffer: pair elements are laid out as
         (L, Bp/64, C/W, 64, 2)."""
         B, L, Cc = a.shape
-        out = torch.empty((L, Cc // W, Bp, W), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_pack_lanes(a.data_ptr(), out.data_ptr(), B, Bp, L, Cc, W, self.stream),
-                   "gym_pack_lanes")
+        out = self._buf(L, Cc // W, Bp, W)
+        self._call("gym_pack_lanes", a, out, B, Bp, L, Cc, W)
         return out
 
     def unpack(self, soa: torch.Tensor, B: int, soa1: torch.Tensor | None = None,
                sel: torch.Tensor | None = None) -> torch.Tensor:
         """SoA (L, P, Bp, W) -> lane-major (B, L, P*W); lane b reads soa1 where sel[b] != 0."""
         L, P, Bp, W = soa.shape
-        out = torch.empty((B, L, P * W), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_unpack_lanes(soa.data_ptr(), _lib.ptr(soa1), _lib.ptr(sel), out.data_ptr(), B, Bp,
-                                             L, P * W, W, self.stream), "gym_unpack_lanes")
+        check_select(soa, soa1, sel, B)
+        out = self._buf(B, L, P * W)
+        self._call("gym_unpack_lanes", soa, soa1, sel, out, B, Bp, L, P * W, W)
         return out
+
+    def unpack_gains(self, K1: torch.Tensor, B: int) -> torch.Tensor:
+        """The stored gain row K1 (T, 2, Bp, 2) (pairs; row 0 of every gain is zero) -> K (B,T,2,4)."""
+        T, _, Bp, _ = K1.shape
+        K = self._buf(B, T, 2, 4)
+        self._call("gym_unpack_gains", K1, K, B, Bp, T)
+        return K
 
     def refs(self, x_ref, u_ref, per_lane: bool = False):
         """(x_ref (N,4), u_ref (N-1,2)) on the device, u_ref trimmed / checked as newton_Algorithm does; with
@@ -149,46 +191,50 @@ class AcrobotEngine:
 
     def continuous_dynamics(self, x, u) -> torch.Tensor:
         x, u, n = self._points(x, u)
-        out = torch.empty((n, 4), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_continuous_dynamics(C.byref(self.model), x.data_ptr(), u.data_ptr(), out.data_ptr(),
-                                                    n, self.stream), "gym_continuous_dynamics")
+        out = self._buf(n, 4)
+        self._call("gym_continuous_dynamics", self.model, x, u, out, n)
         return out
 
     def rk4(self, x, u) -> torch.Tensor:
         x, u, n = self._points(x, u)
-        out = torch.empty((n, 4), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_rk4_step(C.byref(self.model), x.data_ptr(), u.data_ptr(), out.data_ptr(), n,
-                                         self.stream), "gym_rk4_step")
+        out = self._buf(n, 4)
+        self._call("gym_rk4_step", self.model, x, u, out, n)
         return out
 
     def jacobians(self, x, u):
         x, u, n = self._points(x, u)
-        A = torch.empty((n, 4, 4), dtype=F64, device=self.device)
-        Bm = torch.empty((n, 4, 2), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_jacobians(C.byref(self.model), x.data_ptr(), u.data_ptr(), A.data_ptr(),
-                                          Bm.data_ptr(), n, self.stream), "gym_jacobians")
+        A, Bm = self._buf(n, 4, 4), self._buf(n, 4, 2)
+        self._call("gym_jacobians", self.model, x, u, A, Bm, n)
         return A, Bm
 
     def stage_cost_derivs(self, x, x_ref, u, u_ref, Q, R, terminal=False):
-        x = self.t(x).reshape(-1, 4); xr = self.t(x_ref).reshape(-1, 4)
+        x = self.t(x).reshape(-1, 4)
         n = x.shape[0]
+        xr = check_rows(self.t(x_ref).reshape(-1, 4), n, (4,), "x_ref")
         Qm = np.ascontiguousarray(np.asarray(Q, float).reshape(4, 4))
-        l = torch.empty(n, dtype=F64, device=self.device)
-        gx = torch.empty((n, 4), dtype=F64, device=self.device)
-        if terminal:
-            u_ = ur_ = gu = None
-            Rm = None
-        else:
-            u_ = self.t(u).reshape(-1, 2); ur_ = self.t(u_ref).reshape(-1, 2)
+        u_ = ur_ = Rm = None
+        if not terminal:
+            u_ = check_rows(self.t(u).reshape(-1, 2), n, (2,), "u")
+            ur_ = check_rows(self.t(u_ref).reshape(-1, 2), n, (2,), "u_ref")
             Rm = np.ascontiguousarray(np.asarray(R, float).reshape(2, 2))
-            gu = torch.empty((n, 2), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_stage_cost_derivs(
-            x.data_ptr(), xr.data_ptr(), _lib.ptr(u_), _lib.ptr(ur_), Qm.ctypes.data,
-            None if Rm is None else Rm.ctypes.data, int(bool(terminal)), l.data_ptr(), gx.data_ptr(), _lib.ptr(gu),
-            n, self.stream), "gym_stage_cost_derivs")
+        l, gx, gu = self._buf(n), self._buf(n, 4), self._buf(n, 2, want=not terminal)
+        self._call("gym_stage_cost_derivs", x, xr, u_, ur_, Qm, Rm, int(bool(terminal)), l, gx, gu, n)
         return l, gx, gu
 
     # ----------------------------------------------------------------- trajectory kernels
+    def _trajectory(self, x, u, x_ref, u_ref, sigma=None):
+        """The prelude of the trajectory methods: x (B,N,4), u (B,>=N-1,2) to the device, check_trajectory's size
+        rules against the shared reference (already on the device) and ``sigma`` where passed, then x and u packed.
+        Returns (xs, us, B, Bp, N)."""
+        x = self.t(x); u = self.t(u)
+        B, N = check_trajectory(x, u, x_ref, u_ref, sigma)
+        Bp = padded(B)
+        return self.pack(x, Bp), self.pack(u, Bp, W=1), B, Bp, N
+
+    def _gains(self, K, sigma, B, Bp, N):
+        """K (B,N-1,2,4) and sigma (on the device, checked by _trajectory) packed: (Ks, ss)."""
+        return self.pack(self.t(K).reshape(B, N - 1, 8), Bp), self.pack(sigma, Bp, W=1)
+
     def rollout_open_loop(self, x0, u, x_ref, u_ref):
         """simulate_open_loop (+ total_cost): x0 (B,4), u (B,T,2) -> x (B,N,4), J (B,)."""
         x0 = self.t(x0).reshape(-1, 4)
@@ -202,66 +248,45 @@ class AcrobotEngine:
             raise ValueError(f"u must be ({B},{N - 1},2), got {tuple(u.shape)}")
         Bp = padded(B)
         us = self.pack(u, Bp, W=1)
-        xs = torch.empty((N, 2, Bp, 2), dtype=F64, device=self.device)
-        J = torch.empty(Bp, dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_rollout_open_loop(C.byref(self.model), C.byref(self._w), x0.data_ptr(),
-                                                  us.data_ptr(), x_ref.data_ptr(), u_ref.data_ptr(), xs.data_ptr(),
-                                                  J.data_ptr(), B, Bp, N, self.stream), "gym_rollout_open_loop")
+        xs, J = self._buf(N, 2, Bp, 2), self._buf(Bp)
+        self._call("gym_rollout_open_loop", self.model, self._w, x0, us, x_ref, u_ref, xs, J, B, Bp, N)
         return self.unpack(xs, B), J[:B]
 
     def closed_loop(self, x, u, K, sigma, gamma, x_ref, u_ref):
         """forward_closed_loop_update (+ total_cost of the result), full gains K (B,T,2,4)."""
-        x = self.t(x); u = self.t(u); K = self.t(K); sigma = self.t(sigma)
-        B, N, _ = x.shape
-        T = N - 1
+        sigma, gamma = self.t(sigma), self.t(gamma)
         x_ref, u_ref = self.refs(x_ref, u_ref)
-        Bp = padded(B)
-        g = torch.zeros(Bp, dtype=F64, device=self.device)
-        g[:B] = self.t(gamma).reshape(-1).expand(B) if self.t(gamma).numel() == 1 else self.t(gamma).reshape(B)
-        xs, us = self.pack(x, Bp), self.pack(u, Bp, W=1)
-        Ks = self.pack(K.reshape(B, T, 8), Bp)
-        ss = self.pack(sigma, Bp, W=1)
-        xn = torch.empty_like(xs); un = torch.empty_like(us)
-        J = torch.empty(Bp, dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_closed_loop(C.byref(self.model), C.byref(self._w), xs.data_ptr(), us.data_ptr(),
-                                            Ks.data_ptr(), ss.data_ptr(), g.data_ptr(), x_ref.data_ptr(),
-                                            u_ref.data_ptr(), xn.data_ptr(), un.data_ptr(), J.data_ptr(), B, Bp, N,
-                                            self.stream), "gym_closed_loop")
+        xs, us, B, Bp, N = self._trajectory(x, u, x_ref, u_ref, sigma)
+        g = self._buf(Bp, zero=True)
+        g[:B] = gamma.reshape(-1).expand(B) if gamma.numel() == 1 else gamma.reshape(B)
+        Ks, ss = self._gains(K, sigma, B, Bp, N)
+        xn, un, J = self._buf(*xs.shape), self._buf(*us.shape), self._buf(Bp)
+        self._call("gym_closed_loop", self.model, self._w, xs, us, Ks, ss, g, x_ref, u_ref, xn, un, J, B, Bp, N)
         return self.unpack(xn, B), self.unpack(un, B), J[:B]
 
     def gamma_sweep(self, x, u, K, sigma, gammas, x_ref, u_ref) -> torch.Tensor:
         """J(gamma_g) of forward_closed_loop_update + total_cost for each lane and step size (the reference's
         Armijo line-search curve, plot_armijo_line_search :258-264): x (B,N,4), u (B,T,2), K (B,T,2,4),
         sigma (B,T,2), gammas (G,) -> (B, G)."""
-        x = self.t(x); u = self.t(u); K = self.t(K); sigma = self.t(sigma)
+        sigma = self.t(sigma)
         g = self.t(gammas).reshape(-1)
-        B, N, _ = x.shape
-        T = N - 1
         G = int(g.numel())
         if G < 1:
             raise ValueError("gamma_sweep needs at least one step size")
         x_ref, u_ref = self.refs(x_ref, u_ref)
-        Bp = padded(B)
-        xs, us = self.pack(x, Bp), self.pack(u, Bp, W=1)
-        Ks = self.pack(K.reshape(B, T, 8), Bp)
-        ss = self.pack(sigma, Bp, W=1)
-        J = torch.empty((G, Bp), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_gamma_sweep(C.byref(self.model), C.byref(self._w), xs.data_ptr(), us.data_ptr(),
-                                            Ks.data_ptr(), ss.data_ptr(), g.data_ptr(), G, x_ref.data_ptr(),
-                                            u_ref.data_ptr(), J.data_ptr(), B, Bp, N, self.stream), "gym_gamma_sweep")
+        xs, us, B, Bp, N = self._trajectory(x, u, x_ref, u_ref, sigma)
+        Ks, ss = self._gains(K, sigma, B, Bp, N)
+        J = self._buf(G, Bp)
+        self._call("gym_gamma_sweep", self.model, self._w, xs, us, Ks, ss, g, G, x_ref, u_ref, J, B, Bp, N)
         return J[:, :B].t()
 
     def total_cost(self, x, u, x_ref, u_ref, Q, R, QT):
-        x = self.t(x); u = self.t(u)
-        B, N, _ = x.shape
-        x_ref = self.t(x_ref); u_ref = self.t(u_ref)[: N - 1].contiguous()
-        Bp = padded(B)
-        xs, us = self.pack(x, Bp), self.pack(u, Bp, W=1)
+        x_ref = self.t(x_ref); u_ref = self.t(u_ref)
+        xs, us, B, Bp, N = self._trajectory(x, u, x_ref, u_ref)
+        u_ref = u_ref[: N - 1].contiguous()
         mats = [np.ascontiguousarray(np.asarray(M, float)) for M in (Q, R, QT)]
-        J = torch.empty(Bp, dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_total_cost(xs.data_ptr(), us.data_ptr(), x_ref.data_ptr(), u_ref.data_ptr(),
-                                           mats[0].ctypes.data, mats[1].ctypes.data, mats[2].ctypes.data,
-                                           J.data_ptr(), B, Bp, N, self.stream), "gym_total_cost")
+        J = self._buf(Bp)
+        self._call("gym_total_cost", xs, us, x_ref, u_ref, *mats, J, B, Bp, N)
         return J[:B]
 
     def backward(self, x, u, x_ref, u_ref, want_lambda=False, check_gains=True):
@@ -269,39 +294,23 @@ class AcrobotEngine:
         ``check_gains=False``: the caller uses only lambda (compute_costate_trajectory), which needs no G^-1."""
         if check_gains:
             self.weights.require_gain_solvable()
-        x = self.t(x); u = self.t(u)
-        B, N, _ = x.shape
-        T = N - 1
         x_ref, u_ref = self.refs(x_ref, u_ref)
-        Bp = padded(B)
-        xs, us = self.pack(x, Bp), self.pack(u, Bp, W=1)
-        K1 = torch.empty((T, 2, Bp, 2), dtype=F64, device=self.device)
-        sg = torch.empty((T, 2, Bp, 1), dtype=F64, device=self.device)
-        dJ = torch.empty(Bp, dtype=F64, device=self.device)
-        sm = torch.empty(Bp, dtype=F64, device=self.device)
-        lam = torch.empty((N, 2, Bp, 2), dtype=F64, device=self.device) if want_lambda else None
-        _lib.check(self.lib.gym_backward_sweep(C.byref(self.model), C.byref(self._w), xs.data_ptr(), us.data_ptr(),
-                                               x_ref.data_ptr(), u_ref.data_ptr(), K1.data_ptr(), sg.data_ptr(),
-                                               dJ.data_ptr(), sm.data_ptr(), _lib.ptr(lam), B, Bp, N, self.stream),
-                   "gym_backward_sweep")
-        K = torch.empty((B, T, 2, 4), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_unpack_gains(K1.data_ptr(), K.data_ptr(), B, Bp, T, self.stream), "gym_unpack_gains")
-        return K, self.unpack(sg, B), dJ[:B], sm[:B], (self.unpack(lam, B) if want_lambda else None)
+        xs, us, B, Bp, N = self._trajectory(x, u, x_ref, u_ref)
+        T = N - 1
+        K1, sg, dJ, sm = self._buf(T, 2, Bp, 2), self._buf(T, 2, Bp, 1), self._buf(Bp), self._buf(Bp)
+        lam = self._buf(N, 2, Bp, 2, want=want_lambda)
+        self._call("gym_backward_sweep", self.model, self._w, xs, us, x_ref, u_ref, K1, sg, dJ, sm, lam, B, Bp, N)
+        return (self.unpack_gains(K1, B), self.unpack(sg, B), dJ[:B], sm[:B],
+                self.unpack(lam, B) if want_lambda else None)
 
     def linearize(self, x, u, x_ref, u_ref):
         """build_stage_lists: A_d (B,T,4,4), B_d (B,T,4,2), q (B,T,4), r (B,T,2), q_T (B,4)."""
-        x = self.t(x); u = self.t(u)
-        B, N, _ = x.shape
-        T = N - 1
         x_ref, u_ref = self.refs(x_ref, u_ref)
-        Bp = padded(B)
-        xs, us = self.pack(x, Bp), self.pack(u, Bp, W=1)
-        e = lambda *s: torch.empty(s, dtype=F64, device=self.device)  # noqa: E731
-        Ad, Bd, q, r, qT = e(T, 16, Bp), e(T, 8, Bp), e(T, 4, Bp), e(T, 2, Bp), e(4, Bp)
-        _lib.check(self.lib.gym_linearize(C.byref(self.model), C.byref(self._w), xs.data_ptr(), us.data_ptr(),
-                                          x_ref.data_ptr(), u_ref.data_ptr(), Ad.data_ptr(), Bd.data_ptr(),
-                                          q.data_ptr(), r.data_ptr(), qT.data_ptr(), B, Bp, N, self.stream),
-                   "gym_linearize")
+        xs, us, B, Bp, N = self._trajectory(x, u, x_ref, u_ref)
+        T = N - 1
+        Ad, Bd, q, r = self._buf(T, 16, Bp), self._buf(T, 8, Bp), self._buf(T, 4, Bp), self._buf(T, 2, Bp)
+        qT = self._buf(4, Bp)
+        self._call("gym_linearize", self.model, self._w, xs, us, x_ref, u_ref, Ad, Bd, q, r, qT, B, Bp, N)
         lm = lambda a, *s: a[..., :B].permute(-1, *range(a.ndim - 1)).reshape(B, *s)  # noqa: E731
         return lm(Ad, T, 4, 4), lm(Bd, T, 4, 2), lm(q, T, 4), lm(r, T, 2), lm(qT, 4)
 
@@ -314,56 +323,51 @@ class AcrobotEngine:
         def soa(a, shape_tail):  # (B,T,*tail) or broadcastable -> (T, prod(tail), Bp)
             a = self.t(a).expand(B, T, *shape_tail) if a is not None else None
             n = int(np.prod(shape_tail))
-            out = torch.zeros((T, n, Bp), dtype=F64, device=self.device)
+            out = self._buf(T, n, Bp, zero=True)
             out[:, :, :B] = a.reshape(B, T, n).permute(1, 2, 0)
             return out
 
         def soa_t(a, shape_tail):
             a = self.t(a).expand(B, *shape_tail)
             n = int(np.prod(shape_tail))
-            out = torch.zeros((n, Bp), dtype=F64, device=self.device)
+            out = self._buf(n, Bp, zero=True)
             out[:, :B] = a.reshape(B, n).T
             return out
 
         As, Bs, Qs, Rs, Ss = soa(A, (4, 4)), soa(Bm, (4, 2)), soa(Q, (4, 4)), soa(R, (2, 2)), soa(S, (2, 4))
         qs, rs, QTs, qTs = soa(q, (4,)), soa(r, (2,)), soa_t(QT, (4, 4)), soa_t(qT, (4,))
-        K = torch.empty((T, 8, Bp), dtype=F64, device=self.device)
-        sg = torch.empty((T, 2, Bp), dtype=F64, device=self.device)
-        dJ = torch.empty(Bp, dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_riccati_general(As.data_ptr(), Bs.data_ptr(), Qs.data_ptr(), Rs.data_ptr(),
-                                                Ss.data_ptr(), qs.data_ptr(), rs.data_ptr(), QTs.data_ptr(),
-                                                qTs.data_ptr(), K.data_ptr(), sg.data_ptr(), dJ.data_ptr(), B, Bp, T,
-                                                self.stream), "gym_riccati_general")
+        K, sg, dJ = self._buf(T, 8, Bp), self._buf(T, 2, Bp), self._buf(Bp)
+        self._call("gym_riccati_general", As, Bs, Qs, Rs, Ss, qs, rs, QTs, qTs, K, sg, dJ, B, Bp, T)
         return (K[..., :B].permute(2, 0, 1).reshape(B, T, 2, 4), sg[..., :B].permute(2, 0, 1).contiguous(),
                 dJ[:B])
 
     # ------------------------------------------------------------------ LQR / MPC trackers
+    def _stages(self, A, Bm, A_pad, B_pad):
+        """The stage arrays of tv_lqr_gains / lq_forward on the device: A (S,4,4), Bm (>=S,4,2) and the optional
+        pad pair (None where not given)."""
+        A = self.t(A).reshape(-1, 4, 4)
+        Bm = check_rows(self.t(Bm).reshape(-1, 4, 2), A.shape[0], (4, 2), "Bm")
+        return (A, Bm, None if A_pad is None else self.t(A_pad).reshape(4, 4),
+                None if B_pad is None else self.t(B_pad).reshape(4, 2))
+
     def tv_lqr_gains(self, A, Bm, Q, R, QT, L: int, nwin: int = 1, all_gains: bool = True, A_pad=None,
                      B_pad=None, discretize: bool = False) -> torch.Tensor:
         """Windowed time-varying LQR gains (gym_tv_lqr_gains): stages A (S,4,4), B (S,4,2) on the device.
         all_gains: (L-1,2,4) gains of window 0; else (nwin,2,4) first gains of windows 0..nwin-1."""
-        A = self.t(A).reshape(-1, 4, 4); Bm = self.t(Bm).reshape(-1, 4, 2)
-        S = A.shape[0]
-        Ap = None if A_pad is None else self.t(A_pad).reshape(4, 4)
-        Bp_ = None if B_pad is None else self.t(B_pad).reshape(4, 2)
+        A, Bm, Ap, Bp_ = self._stages(A, Bm, A_pad, B_pad)
         Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
         QTd = self.t(QT).reshape(4, 4)                 # device: e.g. dare_fixed_point's P, no host round trip
-        out = torch.empty(((L - 1) if all_gains else nwin, 2, 4), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_tv_lqr_gains(A.data_ptr(), Bm.data_ptr(), S, _lib.ptr(Ap), _lib.ptr(Bp_),
-                                             Qh.ctypes.data, Rh.ctypes.data, QTd.data_ptr(), int(L), int(nwin),
-                                             int(bool(all_gains)), int(bool(discretize)), self.dt, out.data_ptr(),
-                                             self.stream), "gym_tv_lqr_gains")
+        out = self._buf((L - 1) if all_gains else nwin, 2, 4)
+        self._call("gym_tv_lqr_gains", A, Bm, A.shape[0], Ap, Bp_, Qh, Rh, QTd, int(L), int(nwin),
+                   int(bool(all_gains)), int(bool(discretize)), self.dt, out)
         return out
 
     def dare_fixed_point(self, A, Bm, Q, R, max_iter: int = 1000, tol: float = 1e-6):
         """compute_P_inf on the device: returns (P (4,4), iterations (1,) int32), both device tensors (no sync)."""
         A = self.t(A).reshape(4, 4); Bm = self.t(Bm).reshape(4, 2)
         Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
-        P = torch.empty((4, 4), dtype=F64, device=self.device)
-        it = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.gym_dare_fixed_point(A.data_ptr(), Bm.data_ptr(), Qh.ctypes.data, Rh.ctypes.data,
-                                                 int(max_iter), float(tol), P.data_ptr(), it.data_ptr(), self.stream),
-                   "gym_dare_fixed_point")
+        P, it = self._buf(4, 4), self._buf(1, dtype=I32, zero=True)
+        self._call("gym_dare_fixed_point", A, Bm, Qh, Rh, int(max_iter), float(tol), P, it)
         return P, it
 
     def _mpc_gains(self, every, x_ref, u_ref, x_f, u_f, Q, R, L, nwin, max_iter, tol):
@@ -374,14 +378,10 @@ class AcrobotEngine:
         if u_ref.shape[0] < S:
             raise ValueError(f"u_ref must hold {S} stages, got {u_ref.shape[0]}")
         Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
-        K = torch.empty((nwin, int(L) - 1, 2, 4) if every else (nwin, 2, 4), dtype=F64, device=self.device)
-        P = torch.empty((4, 4), dtype=F64, device=self.device)
-        it = torch.zeros(1, dtype=torch.int32, device=self.device)
-        name = "gym_mpc_gains_all" if every else "gym_mpc_gains"
-        _lib.check(getattr(self.lib, name)(C.byref(self.model), x_ref.data_ptr(), u_ref.data_ptr(), S, x_f.data_ptr(),
-                                           u_f.data_ptr(), Qh.ctypes.data, Rh.ctypes.data, int(L), int(nwin),
-                                           int(max_iter), float(tol), K.data_ptr(), P.data_ptr(), it.data_ptr(),
-                                           self.stream), name)
+        K = self._buf(nwin, int(L) - 1, 2, 4) if every else self._buf(nwin, 2, 4)
+        P, it = self._buf(4, 4), self._buf(1, dtype=I32, zero=True)
+        self._call("gym_mpc_gains_all" if every else "gym_mpc_gains", self.model, x_ref, u_ref, S, x_f, u_f, Qh, Rh,
+                   int(L), int(nwin), int(max_iter), float(tol), K, P, it)
         return K, P, it
 
     def mpc_gains(self, x_ref, u_ref, x_f, u_f, Q, R, L: int, nwin: int, max_iter: int = 1000, tol: float = 1e-6):
@@ -390,17 +390,19 @@ class AcrobotEngine:
         (K0 (nwin,2,4), Q_T (4,4), iterations (1,) int32); no host synchronisation."""
         return self._mpc_gains(False, x_ref, u_ref, x_f, u_f, Q, R, L, nwin, max_iter, tol)
 
+    def mpc_gains_all(self, x_ref, u_ref, x_f, u_f, Q, R, L: int, nwin: int, max_iter: int = 1000,
+                      tol: float = 1e-6):
+        """gym_mpc_gains_all: mpc_gains with every stage's gain of every window.  Returns device tensors
+        (K_all (nwin,L-1,2,4), Q_T (4,4), iterations (1,) int32); K_all[:, 0] is mpc_gains' K0 bit for bit."""
+        return self._mpc_gains(True, x_ref, u_ref, x_f, u_f, Q, R, L, nwin, max_iter, tol)
+
     def lq_forward(self, A, Bm, K, x0, L: int, A_pad=None, B_pad=None, discretize: bool = False):
         """One window's LQ forward pass: X (L,4), U (L-1,2)."""
-        A = self.t(A).reshape(-1, 4, 4); Bm = self.t(Bm).reshape(-1, 4, 2)
-        Ap = None if A_pad is None else self.t(A_pad).reshape(4, 4)
-        Bp_ = None if B_pad is None else self.t(B_pad).reshape(4, 2)
-        K = self.t(K).reshape(-1, 2, 4); x0 = self.t(x0).reshape(4)
-        X = torch.empty((L, 4), dtype=F64, device=self.device)
-        U = torch.empty((L - 1, 2), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_lq_forward(A.data_ptr(), Bm.data_ptr(), A.shape[0], _lib.ptr(Ap), _lib.ptr(Bp_),
-                                           int(bool(discretize)), self.dt, K.data_ptr(), x0.data_ptr(), int(L),
-                                           X.data_ptr(), U.data_ptr(), self.stream), "gym_lq_forward")
+        A, Bm, Ap, Bp_ = self._stages(A, Bm, A_pad, B_pad)
+        K = check_rows(self.t(K).reshape(-1, 2, 4), int(L) - 1, (2, 4), "K")
+        x0 = self.t(x0).reshape(4)
+        X, U = self._buf(L, 4), self._buf(L - 1, 2)
+        self._call("gym_lq_forward", A, Bm, A.shape[0], Ap, Bp_, int(bool(discretize)), self.dt, K, x0, int(L), X, U)
         return X, U
 
     def track_rollout(self, x0, x_ff, u_ff, K, single: bool = False):
@@ -412,30 +414,37 @@ class AcrobotEngine:
         if u_ff.shape[0] != N - 1 or K.shape[0] != N - 1:
             raise ValueError(f"feed-forward / gains must hold {N - 1} stages, got {u_ff.shape[0]} / {K.shape[0]}")
         B = x0.shape[0]
-        x = torch.empty((B, N, 4), dtype=F64, device=self.device)
-        u = torch.empty((B, N - 1, 2), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_track_rollout_ex(C.byref(self.model), x0.data_ptr(), x_ff.data_ptr(),
-                                                 u_ff.data_ptr(), K.data_ptr(), B, N,
-                                                 _lib.TRACK_SINGLE if single else 0, x.data_ptr(), u.data_ptr(),
-                                                 self.stream), "gym_track_rollout_ex")
+        x, u = self._buf(B, N, 4), self._buf(B, N - 1, 2)
+        self._call("gym_track_rollout_ex", self.model, x0, x_ff, u_ff, K, B, N, _lib.TRACK_SINGLE if single else 0,
+                   x, u)
         return x, u
 
-    # ------------------------------------------------------------- torque-limited MPC (box QP)
-    def mpc_gains_all(self, x_ref, u_ref, x_f, u_f, Q, R, L: int, nwin: int, max_iter: int = 1000,
-                      tol: float = 1e-6):
-        """gym_mpc_gains_all: mpc_gains with every stage's gain of every window.  Returns device tensors
-        (K_all (nwin,L-1,2,4), Q_T (4,4), iterations (1,) int32); K_all[:, 0] is mpc_gains' K0 bit for bit."""
-        return self._mpc_gains(True, x_ref, u_ref, x_f, u_f, Q, R, L, nwin, max_iter, tol)
-
+    # ------------------------------------------------------------- caller-owned workspaces
     def _ws_bytes(self, name: str, *sizes) -> int:
         """What the workspace-size entry point ``name`` answers for ``sizes``."""
         need = C.c_int64()
-        _lib.check(getattr(self.lib, name)(*(int(v) for v in sizes), C.byref(need)), name)
+        self._call(name, *(int(v) for v in sizes), C.byref(need), stream=False)
         return need.value
 
+    def _workspace(self, ws, name: str | None = None, *sizes, holds: str | None = None):
+        """The caller's workspace ``ws``, or a fresh one of the size the entry point ``name`` answers for ``sizes``
+        (no ``name``: the workspace carries an earlier call's results, so the caller must give it), and its byte
+        count: (ws, bytes).  The library refuses a short workspace; with ``holds`` (what it is to hold) the host
+        does, before the launch."""
+        if ws is None and name is None:
+            raise TypeError("this call needs the workspace an earlier call filled")
+        need = self._ws_bytes(name, *sizes) if ws is None or holds else None
+        if ws is None:
+            ws = self._buf(need, dtype=U8)
+        ws_bytes = ws.numel() * ws.element_size()
+        if holds and ws_bytes < need:
+            raise ValueError(f"the workspace holds {ws_bytes} bytes, {holds} need {need}")
+        return ws, ws_bytes
+
+    # ------------------------------------------------------------- torque-limited MPC (box QP)
     def mpc_box_workspace(self, B: int, L: int, rows: int) -> torch.Tensor:
         """The caller-owned workspace of gym_mpc_box_qp (rows = stages given) / gym_mpc_box_rollout (rows = N)."""
-        return torch.empty(self._ws_bytes("gym_mpc_box_workspace", B, L, rows), dtype=torch.uint8, device=self.device)
+        return self._workspace(None, "gym_mpc_box_workspace", B, L, rows)[0]
 
     def mpc_box_qp(self, A, Bm, u_ref, Q, R, QT, x0, L: int, tau_max: float, max_qp_iters: int = 32, ws=None):
         """gym_mpc_box_qp: the torque-limited QP of one window for a batch x0 (B,4).  Stages A (S,4,4), Bm (S,4,2),
@@ -455,15 +464,11 @@ class AcrobotEngine:
         QTd = self.t(QT).reshape(4, 4)
         x0 = self.t(x0).reshape(-1, 4)
         B = x0.shape[0]
-        ws = self.mpc_box_workspace(B, L, S) if ws is None else ws
-        U = torch.empty((B, L - 1, 2), dtype=F64, device=self.device)
-        X = torch.empty((B, L, 4), dtype=F64, device=self.device)
-        it = torch.empty(B, dtype=torch.int32, device=self.device)
-        conv = torch.empty(B, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.gym_mpc_box_qp(A.ctypes.data, Bm.ctypes.data, ur.ctypes.data, S, Qh.ctypes.data,
-                                           Rh.ctypes.data, QTd.data_ptr(), x0.data_ptr(), B, L, float(tau_max),
-                                           int(max_qp_iters), ws.data_ptr(), ws.numel(), U.data_ptr(), X.data_ptr(),
-                                           it.data_ptr(), conv.data_ptr(), self.stream), "gym_mpc_box_qp")
+        ws, ws_bytes = self._workspace(ws, "gym_mpc_box_workspace", B, L, S)
+        U, X = self._buf(B, L - 1, 2), self._buf(B, L, 4)
+        it, conv = self._buf(B, dtype=I32), self._buf(B, dtype=I32)
+        self._call("gym_mpc_box_qp", A, Bm, ur, S, Qh, Rh, QTd, x0, B, L, float(tau_max), int(max_qp_iters), ws,
+                   ws_bytes, U, X, it, conv)
         return U, X, it, conv
 
     def mpc_box_rollout(self, x0, x_ref, u_ref, x_f, u_f, Q, R, QT, K_all, tau_max: float, max_qp_iters: int = 32,
@@ -483,23 +488,17 @@ class AcrobotEngine:
         L = K_all.shape[1] + 1
         Qh, Rh = host_mat(Q, 4, "Q"), host_mat(R, 2, "R")
         B = x0.shape[0]
-        ws = self.mpc_box_workspace(B, L, N) if ws is None else ws
-        x = torch.empty((B, N, 4), dtype=F64, device=self.device)
-        u = torch.empty((B, N - 1, 2), dtype=F64, device=self.device)
-        it = torch.empty((B, N - 1), dtype=torch.int32, device=self.device)
-        unconv = torch.empty(B, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.gym_mpc_box_rollout(C.byref(self.model), x0.data_ptr(), x_ref.data_ptr(),
-                                                u_ref.data_ptr(), x_f.data_ptr(), u_f.data_ptr(), Qh.ctypes.data,
-                                                Rh.ctypes.data, QTd.data_ptr(), K_all.data_ptr(), B, N, L,
-                                                float(tau_max), int(max_qp_iters), ws.data_ptr(), ws.numel(),
-                                                x.data_ptr(), u.data_ptr(), it.data_ptr(), unconv.data_ptr(),
-                                                self.stream), "gym_mpc_box_rollout")
+        ws, ws_bytes = self._workspace(ws, "gym_mpc_box_workspace", B, L, N)
+        x, u = self._buf(B, N, 4), self._buf(B, N - 1, 2)
+        it, unconv = self._buf(B, N - 1, dtype=I32), self._buf(B, dtype=I32)
+        self._call("gym_mpc_box_rollout", self.model, x0, x_ref, u_ref, x_f, u_f, Qh, Rh, QTd, K_all, B, N, L,
+                   float(tau_max), int(max_qp_iters), ws, ws_bytes, x, u, it, unconv)
         return x, u, it, unconv
 
     # ------------------------------------------------------------- per-lane LQR tracking
     def lqr_lanes_workspace(self, B: int, N: int) -> torch.Tensor:
         """The caller-owned workspace of gym_lqr_lanes_gains / gym_lqr_lanes_rollout for B lanes of N knots."""
-        return torch.empty(self._ws_bytes("gym_lqr_lanes_workspace", B, N), dtype=torch.uint8, device=self.device)
+        return self._workspace(None, "gym_lqr_lanes_workspace", B, N)[0]
 
     def lqr_lanes_gains(self, x_opt, u_opt, Q, R, QT, gains: bool = True, ws=None):
         """gym_lqr_lanes_gains: solve_LQR_tracking per lane along x_opt (B,N,4), u_opt (B,N-1,2).  Returns (ws, K):
@@ -508,11 +507,9 @@ class AcrobotEngine:
         B, N = check_lane_trajectories(x_opt, u_opt)
         Rh = check_diagonal_R(R, "per-lane LQR tracking")
         Qh, QTh = check_sym_weight(Q, "Q"), check_sym_weight(QT, "QT")
-        ws = self.lqr_lanes_workspace(B, N) if ws is None else ws
-        K = torch.empty((B, N - 1, 2, 4), dtype=F64, device=self.device) if gains else None
-        _lib.check(self.lib.gym_lqr_lanes_gains(C.byref(self.model), x_opt.data_ptr(), u_opt.data_ptr(), B, N,
-                                                Qh.ctypes.data, Rh.ctypes.data, QTh.ctypes.data, ws.data_ptr(),
-                                                ws.numel(), _lib.ptr(K), self.stream), "gym_lqr_lanes_gains")
+        ws, ws_bytes = self._workspace(ws, "gym_lqr_lanes_workspace", B, N)
+        K = self._buf(B, N - 1, 2, 4, want=gains)
+        self._call("gym_lqr_lanes_gains", self.model, x_opt, u_opt, B, N, Qh, Rh, QTh, ws, ws_bytes, K)
         return ws, K
 
     def lqr_lanes_rollout(self, ws, x0, N: int, trajectories: bool = True):
@@ -521,12 +518,10 @@ class AcrobotEngine:
         x0 = self.t(x0)
         check_lane_starts(x0)
         B, P, N = x0.shape[0], x0.shape[1], int(N)
-        x = torch.empty((B, P, N, 4), dtype=F64, device=self.device) if trajectories else None
-        u = torch.empty((B, P, N - 1, 2), dtype=F64, device=self.device) if trajectories else None
-        summary = torch.empty((3, B, P), dtype=F64, device=self.device)
-        _lib.check(self.lib.gym_lqr_lanes_rollout(C.byref(self.model), x0.data_ptr(), B, P, N, ws.data_ptr(),
-                                                  ws.numel(), _lib.ptr(x), _lib.ptr(u), summary.data_ptr(),
-                                                  self.stream), "gym_lqr_lanes_rollout")
+        ws, ws_bytes = self._workspace(ws)
+        x, u = self._buf(B, P, N, 4, want=trajectories), self._buf(B, P, N - 1, 2, want=trajectories)
+        summary = self._buf(3, B, P)
+        self._call("gym_lqr_lanes_rollout", self.model, x0, B, P, N, ws, ws_bytes, x, u, summary)
         return x, u, summary
 
     # ------------------------------------------------------------- per-lane MPC tracking
@@ -541,16 +536,9 @@ class AcrobotEngine:
         Rh = check_diagonal_R(R, "per-lane MPC tracking")
         Qh = check_sym_weight(Q, "Q")
         QTd = check_device_QT(self.t(QT))
-        need = self._ws_bytes("gym_lqr_lanes_workspace", B, N)
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws_bytes = ws.numel() * ws.element_size()
-        if ws_bytes < need:
-            raise ValueError(f"the workspace holds {ws_bytes} bytes, {B} lanes of {N} knots need {need}")
-        K = torch.empty((B, N - 1, 2, 4), dtype=F64, device=self.device) if gains else None
-        _lib.check(self.lib.gym_mpc_lanes_gains(C.byref(self.model), x_opt.data_ptr(), u_opt.data_ptr(), B, N, L,
-                                                Qh.ctypes.data, Rh.ctypes.data, QTd.data_ptr(), ws.data_ptr(),
-                                                ws_bytes, _lib.ptr(K), self.stream), "gym_mpc_lanes_gains")
+        ws, ws_bytes = self._workspace(ws, "gym_lqr_lanes_workspace", B, N, holds=f"{B} lanes of {N} knots")
+        K = self._buf(B, N - 1, 2, 4, want=gains)
+        self._call("gym_mpc_lanes_gains", self.model, x_opt, u_opt, B, N, L, Qh, Rh, QTd, ws, ws_bytes, K)
         return ws, K
 
     # ------------------------------------------------------------- per-lane torque-limited MPC tracking
@@ -582,34 +570,61 @@ class AcrobotEngine:
         if max_ws_bytes is None:
             max_ws_bytes = int(self.BOX_LANES_WS_SHARE * torch.cuda.mem_get_info(self.device)[0])
         chunk = max(1, min(B, int(max_ws_bytes) // per_lane))
-        ws = torch.empty(chunk * per_lane, dtype=torch.uint8, device=self.device)
-        x = torch.empty((B, P, N, 4), dtype=F64, device=self.device) if trajectories else None
-        u = torch.empty((B, P, N - 1, 2), dtype=F64, device=self.device) if trajectories else None
-        it = torch.empty((B, P, N - 1), dtype=torch.int32, device=self.device) if trajectories else None
-        summary = torch.empty((3, B, P), dtype=F64, device=self.device)
-        unconv = torch.empty((B, P), dtype=torch.int32, device=self.device)
+        ws = self._buf(chunk * per_lane, dtype=U8)
+        x, u = self._buf(B, P, N, 4, want=trajectories), self._buf(B, P, N - 1, 2, want=trajectories)
+        it = self._buf(B, P, N - 1, dtype=I32, want=trajectories)
+        summary, unconv = self._buf(3, B, P), self._buf(B, P, dtype=I32)
         for b0 in range(0, B, chunk):
             b1 = min(B, b0 + chunk)
-            sm = summary if chunk >= B else torch.empty((3, b1 - b0, P), dtype=F64, device=self.device)
-            _lib.check(self.lib.gym_mpc_box_lanes_rollout(
-                C.byref(self.model), x_opt[b0:b1].data_ptr(), u_opt[b0:b1].data_ptr(), x0[b0:b1].data_ptr(), b1 - b0,
-                P, N, L, Qh.ctypes.data, Rh.ctypes.data, QTd.data_ptr(), float(tau_max), int(max_qp_iters),
-                ws.data_ptr(), ws.numel(), _lib.ptr(None if x is None else x[b0:b1]),
-                _lib.ptr(None if u is None else u[b0:b1]), sm.data_ptr(), _lib.ptr(None if it is None else it[b0:b1]),
-                unconv[b0:b1].data_ptr(), self.stream), "gym_mpc_box_lanes_rollout")
+            part = lambda a: None if a is None else a[b0:b1]  # noqa: E731 -- this chunk's lanes of a lane-major buffer
+            sm = summary if chunk >= B else self._buf(3, b1 - b0, P)
+            self._call("gym_mpc_box_lanes_rollout", self.model, part(x_opt), part(u_opt), part(x0), b1 - b0, P, N, L,
+                       Qh, Rh, QTd, float(tau_max), int(max_qp_iters), ws, ws.numel(), part(x), part(u), sm, part(it),
+                       part(unconv))
             if sm is not summary:
                 summary[:, b0:b1] = sm
         return x, u, summary, it, unconv
 
 
-# ------------------------------------------------------------------ the trackers' argument checks
+# ------------------------------------------------------------------------------------- argument checks
 # Plain functions of shapes and host values (torch tensors and numpy arrays alike): no device, no engine, so the
-# front end (trajectory_tracking.py) refuses a bad call with the same words before it asks for either.
+# front end (trajectory_tracking.py) refuses a bad call with the same words before it asks for either.  The size rules
+# (check_rows, check_trajectory, check_select) ask for at least what the kernel reads: the ABI is given B, Bp, N and
+# bare addresses, so a short buffer would be read past its end; spare trailing rows are never read and pass.
 def host_mat(M, n, name):
     M = np.ascontiguousarray(np.asarray(M, dtype=np.float64))
     if M.shape != (n, n):
         raise ValueError(f"{name} must be {n}x{n}, got {M.shape}")
     return M
+
+
+def check_rows(a, n: int, tail: tuple, name: str):
+    """``a`` (the argument ``name``) holds at least the n rows of shape ``tail`` a kernel reads.  Returns a."""
+    if tuple(a.shape[1:]) != tuple(tail) or a.shape[0] < n:
+        raise ValueError(f"{name} must be (>={n},{','.join(str(v) for v in tail)}), got {tuple(a.shape)}")
+    return a
+
+
+def check_trajectory(x, u, x_ref, u_ref, sigma=None):
+    """Lane trajectories under a shared reference, as the trajectory kernels read them for (B, N): x (B,N,4) with
+    N >= 2, u -- and sigma where passed -- (B,>=N-1,2), x_ref (>=N,4), u_ref (>=N-1,2).  Returns (B, N)."""
+    if x.ndim != 3 or x.shape[2] != 4 or x.shape[1] < 2:
+        raise ValueError(f"x must be (B,N,4) with N >= 2, got {tuple(x.shape)}")
+    B, N = x.shape[0], x.shape[1]
+    for name, a in (("u", u), ("sigma", sigma)):
+        if a is not None and (a.ndim != 3 or a.shape[0] != B or a.shape[1] < N - 1 or a.shape[2] != 2):
+            raise ValueError(f"{name} must be ({B},>={N - 1},2) for x {tuple(x.shape)}, got {tuple(a.shape)}")
+    check_rows(x_ref, N, (4,), "x_ref")
+    check_rows(u_ref, N - 1, (2,), "u_ref")
+    return B, N
+
+
+def check_select(soa, soa1, sel, B: int):
+    """unpack's per-lane select: soa1 shaped like soa, sel int32 with an entry for each of the B lanes."""
+    if soa1 is not None and tuple(soa1.shape) != tuple(soa.shape):
+        raise ValueError(f"soa1 must be {tuple(soa.shape)} like soa, got {tuple(soa1.shape)}")
+    if sel is not None and (sel.dtype != torch.int32 or sel.ndim != 1 or sel.shape[0] < B):
+        raise ValueError(f"sel must be int32 (>={B},), got {sel.dtype} {tuple(sel.shape)}")
 
 
 def check_lane_trajectories(x_opt, u_opt, or_n_rows: bool = False):

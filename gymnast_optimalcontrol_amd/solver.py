@@ -677,10 +677,7 @@ class BatchedNewtonSolver:
 
     def gains(self) -> torch.Tensor:
         """K (B,T,2,4) of every lane's most recent backward sweep."""
-        K = torch.empty((self.B, self.T, 2, 4), dtype=F64, device=self.eng.device)
-        _lib.check(self.eng.lib.gym_unpack_gains(self.K1.data_ptr(), K.data_ptr(), self.B, self.Bp, self.T,
-                                                 self.eng.stream), "gym_unpack_gains")
-        return K
+        return self.eng.unpack_gains(self.K1, self.B)
 
     def controls(self, buf: int) -> torch.Tensor:
         """u (B,T,2) of control buffer ``buf``."""

@@ -279,6 +279,34 @@ def test_backward_sweep_and_linearize_per_lane(wcase, traj, B):
     print(f"DEV backward B={B}: {dev}; linearize A_d {np.abs(lin[0] - Ad).max():.2e}")
 
 
+@pytest.mark.parametrize("B", [3, 65])
+def test_spare_rows_are_invisible(eng, traj, B):
+    """The engine asks for at least the rows a kernel reads: u and sigma of N rows (one spare) under a reference of
+    N + 2 rows give, bit for bit, what the exact-size call gives, on the rows the exact-size call returns.  N = 6;
+    one partial wavefront, and one lane past a full one."""
+    N = 6
+    T = N - 1
+    x, K, gam = traj["x"][:B, :N], traj["K"][:B, :T], traj["gamma"][:B]
+    gammas = np.array([0.3, 1.0])
+    Q, R, QT = dr.gen_dense_weights()
+
+    def results(nu, nxr, nur):
+        u, s, xr, ur = traj["u"][:B, :nu], traj["sigma"][:B, :nu], traj["x_ref"][:nxr], traj["u_ref"][:nur]
+        return dict(closed_loop=eng.closed_loop(x, u, K, s, gam, xr, ur),
+                    gamma_sweep=(eng.gamma_sweep(x, u, K, s, gammas, xr, ur),),
+                    backward=eng.backward(x, u, xr, ur, want_lambda=True), linearize=eng.linearize(x, u, xr, ur),
+                    total_cost=(eng.total_cost(x, u, xr, ur, Q, R, QT),))
+
+    exact, spare = results(T, N, T), results(N, N + 2, N + 1)
+    for name in exact:
+        for i, (a, b) in enumerate(zip(exact[name], spare[name])):
+            a, b = _np(a), _np(b)
+            if name == "closed_loop" and i == 1:          # u_new has as many rows as u; the spare one is not written
+                assert b.shape == (B, N, 2)
+                b = b[:, :T]
+            assert a.shape == b.shape and np.array_equal(a, b), (name, i)
+
+
 # ------------------------------------------------------------------------------------------- dense Riccati
 @pytest.mark.parametrize("B,T", dr.RICCATI_SHAPES + [(4, dr.NMAX)])
 def test_riccati_general_pivoting(eng, kats, B, T):

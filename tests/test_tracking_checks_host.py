@@ -112,6 +112,57 @@ def test_device_QT():
             en.check_device_QT(bad)
 
 
+def test_rows():
+    """At least the rows a kernel reads, of exactly the row shape it reads; spare trailing rows pass."""
+    a = np.zeros((6, 4, 2))
+    assert en.check_rows(a, 6, (4, 2), "Bm") is a and en.check_rows(a, 1, (4, 2), "Bm") is a
+    assert en.check_rows(U[0], 4, (2,), "u_ref").shape == (4, 2) and en.check_rows(a[:0], 0, (4, 2), "Bm").shape[0] == 0
+    with pytest.raises(ValueError, match=r"^Bm must be \(>=7,4,2\), got \(6, 4, 2\)$"):
+        en.check_rows(a, 7, (4, 2), "Bm")
+    for bad in (np.zeros((6, 2, 4)), np.zeros((6, 8)), np.zeros((6, 4, 2, 1)), np.zeros(6)):
+        with pytest.raises(ValueError, match=r"^Bm must be \(>=6,4,2\), got " + _shape(bad)):
+            en.check_rows(bad, 6, (4, 2), "Bm")
+    with pytest.raises(ValueError, match=r"^x_ref must be \(>=5,4\), got \(4, 4\)$"):
+        en.check_rows(np.zeros((4, 4)), 5, (4,), "x_ref")
+
+
+def test_trajectory():
+    """x (B,N,4); u and sigma (B,>=N-1,2); a shared reference of >= N and >= N-1 rows: what the kernels read."""
+    xr, ur, s = np.zeros((5, 4)), np.zeros((4, 2)), np.zeros((3, 4, 2))
+    assert en.check_trajectory(X, U, xr, ur) == (3, 5) and en.check_trajectory(X, U, xr, ur, s) == (3, 5)
+    assert en.check_trajectory(X[:, :2], U[:, :1], xr[:2], ur[:1], s[:, :1]) == (3, 2)
+    spare = np.zeros((3, 5, 2))
+    assert en.check_trajectory(X, spare, np.zeros((7, 4)), np.zeros((6, 2)), spare) == (3, 5)
+    for x in (X[0], X[None], X[..., :3], X[:, :1]):
+        with pytest.raises(ValueError, match=r"^x must be \(B,N,4\) with N >= 2, got " + _shape(x)):
+            en.check_trajectory(x, U, xr, ur)
+    for bad in (U[:2], U[:, :3], U[..., :1], U[0], U[None], np.zeros((4, 4, 2))):   # lanes, rows, channels, rank
+        with pytest.raises(ValueError, match=r"^u must be \(3,>=4,2\) for x \(3, 5, 4\), got " + _shape(bad)):
+            en.check_trajectory(X, bad, xr, ur)
+        with pytest.raises(ValueError, match=r"^sigma must be \(3,>=4,2\) for x \(3, 5, 4\), got " + _shape(bad)):
+            en.check_trajectory(X, U, xr, ur, bad)
+    for bad in (xr[:4], np.zeros((5, 3)), np.zeros((1, 5, 4))):
+        with pytest.raises(ValueError, match=r"^x_ref must be \(>=5,4\), got " + _shape(bad)):
+            en.check_trajectory(X, U, bad, ur)
+    for bad in (ur[:3], np.zeros((4, 1)), np.zeros(4)):
+        with pytest.raises(ValueError, match=r"^u_ref must be \(>=4,2\), got " + _shape(bad)):
+            en.check_trajectory(X, U, xr, bad)
+
+
+def test_select():
+    import torch
+    soa = torch.zeros((5, 2, 64, 2), dtype=torch.float64)
+    sel = torch.zeros(3, dtype=torch.int32)
+    assert en.check_select(soa, None, None, 3) is None and en.check_select(soa, soa.clone(), sel, 3) is None
+    assert en.check_select(soa, soa, torch.zeros(64, dtype=torch.int32), 3) is None
+    for bad in (soa[:4], soa[:, :1], soa[..., :1], soa[0]):
+        with pytest.raises(ValueError, match=r"^soa1 must be \(5, 2, 64, 2\) like soa, got " + _shape(bad)):
+            en.check_select(soa, bad, sel, 3)
+    for bad in (sel[:2], sel.to(torch.int64), sel.to(torch.float64), torch.zeros((3, 1), dtype=torch.int32)):
+        with pytest.raises(ValueError, match=r"^sel must be int32 \(>=3,\), got "):
+            en.check_select(soa, soa, bad, 3)
+
+
 def test_front_end_refuses_through_the_same_checks_before_any_device():
     """trajectory_tracking's torque-limited paths run check_box / check_window first: no engine is made for a refused
     call.  MPC_tracking_lanes names its keywords, so an unknown one is Python's own TypeError."""
