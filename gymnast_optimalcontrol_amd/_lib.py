@@ -29,9 +29,10 @@ EXPORTS = (
     "gym_gamma_sweep", "gym_newton_gamma_sweep",
     "gym_tv_lqr_gains", "gym_dare_fixed_point", "gym_mpc_gains", "gym_lq_forward", "gym_track_rollout", "gym_track_rollout_ex",
     "gym_mpc_gains_all", "gym_mpc_box_workspace", "gym_mpc_box_qp", "gym_mpc_box_rollout",
+    "gym_mpc_box_qp_fallback", "gym_mpc_box_rollout_fallback",
     "gym_lqr_lanes_workspace", "gym_lqr_lanes_gains", "gym_lqr_lanes_rollout",
     "gym_mpc_lanes_gains",
-    "gym_mpc_box_lanes_workspace", "gym_mpc_box_lanes_rollout",
+    "gym_mpc_box_lanes_workspace", "gym_mpc_box_lanes_rollout", "gym_mpc_box_lanes_rollout_fallback",
     "gym_timing_create", "gym_timing_destroy", "gym_timing_collect",
 )
 KERNEL_KINDS = ("backward", "trial", "candidates", "retry", "stats", "phase_odd", "phase_even", "sigma", "run",
@@ -131,6 +132,10 @@ _SIGS = {
     "gym_mpc_box_qp": [_P, _P, _P, _I32, _P, _P, _P, _P, _I64, _I32, _D, _I32, _P, _I64, _P, _P, _P, _P, _P],
     "gym_mpc_box_rollout": [_MP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _P, _I64, _P, _P, _P,
                             _P, _P],
+    "gym_mpc_box_qp_fallback": [_P, _P, _P, _I32, _P, _P, _P, _P, _I64, _I32, _D, _I32, _I32, _P, _I64, _P, _P, _P, _P,
+                                _P],
+    "gym_mpc_box_rollout_fallback": [_MP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _I32, _P, _I64,
+                                     _P, _P, _P, _P, _P],
     "gym_lqr_lanes_workspace": [_I64, _I32, C.POINTER(C.c_int64)],
     "gym_lqr_lanes_gains": [_MP, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _P, _P],
     "gym_lqr_lanes_rollout": [_MP, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P, _P],
@@ -138,6 +143,8 @@ _SIGS = {
     "gym_mpc_box_lanes_workspace": [_I64, _I32, _I32, C.POINTER(C.c_int64)],
     "gym_mpc_box_lanes_rollout": [_MP, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _D, _I32, _P, _I64, _P, _P, _P,
                                   _P, _P, _P],
+    "gym_mpc_box_lanes_rollout_fallback": [_MP, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _D, _I32, _I32, _P, _I64,
+                                           _P, _P, _P, _P, _P, _P],
     "gym_timing_create": [C.POINTER(GymTiming)],
     "gym_timing_destroy": [C.POINTER(GymTiming)],
     "gym_timing_collect": [C.POINTER(GymTiming)],

@@ -1,6 +1,7 @@
 // Torque-limited MPC on ONE shared reference (gym_mpc_box_qp / gym_mpc_box_rollout): the box-QP active set
-// (box_qp_lane and its three passes, which mpc_box_lanes.hpp runs per lane as well), the stage table, the two kernels
-// and the workspace layout.  Part of the tracking_kernels.hip translation unit: included inside its anonymous
+// (box_qp_lane and its three passes, which mpc_box_lanes.hpp runs per lane as well), its opt-in projected-Newton
+// fallback (box_pn_lane; the ..._fallback entry points), the stage table, the kernels (mpc_box_kernels.def.hpp) and
+// the workspace layout.  Part of the tracking_kernels.hip translation unit: included inside its anonymous
 // namespace; gym:: and Dyn come from acrobot_device.hpp, which the .hip includes ahead of the namespace.
 #pragma once
 
@@ -214,14 +215,220 @@ __device__ __forceinline__ bool box_update(const BoxWin& w, int Lm, const M44& Q
     return changed;
 }
 
+// ------------------------------------------------------------------------------------------
+// The fallback (FALLBACK instantiations only): a QP whose active set has not settled after max_it sweeps is continued
+// by projected Newton (Bertsekas) from its clipped iterate u, which is feasible.  One iteration:
+//   gradient   q_t by box_update's costate pass over the stored (x, u); stage t is at lo when u_t <= lo_t and q_t > 0,
+//              at hi when u_t >= hi_t and q_t < 0, free otherwise (box_pn_gradient: whether any state changed)
+//   target     box_backward on these states, unchanged; ubar_t = k_t x_t + d_t along its own states (box_pn_target:
+//              whether a free stage of ubar lies outside its bounds)
+//   search     a = 1, 1/2, ... (kBoxPnTrials at most): u(a) = clip(u + a (ubar - u), lo, hi); the first a with
+//              J(u(a)) <= J(u) + kBoxPnSigma q'(u(a) - u) is taken, the difference of the two costs coming from one
+//              linear rollout (box_pn_trial), and stored with its states (box_pn_store); none: the QP stays
+//              unconverged and returns u
+//   stop       a = 1 taken, no violation, and the next gradient's active set is the one just used: ubar is
+//              stationary on its face with correctly signed multipliers, the active set's own certificate.
+// Slots: q lives in slot 5 and ubar in slot 6 from the gradient to the store (x is dead there: the store rolls the
+// states out again, and every exit ends with a store), so the layout and the workspace sizes do not change.
+// ------------------------------------------------------------------------------------------
+constexpr int kBoxPnTrials = 30;
+constexpr double kBoxPnSigma = 1e-4;
+
+// costate pass over the stored (x, u): q_t -> slot 5, the active set of (u, q) -> the stage states
+__device__ __forceinline__ bool box_pn_gradient(const BoxWin& w, int Lm, const M44& Q, double r, const double* QT,
+                                                double tau, const BoxWs& ws) {
+    double lam[4];
+    {
+        const double x[4] = {ws.at(Lm, 0), ws.at(Lm, 1), ws.at(Lm, 2), ws.at(Lm, 3)};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            lam[i] = 2.0 * (((QT[4 * i] * x[0] + QT[4 * i + 1] * x[1]) + QT[4 * i + 2] * x[2]) + QT[4 * i + 3] * x[3]);
+    }
+    bool changed = false;
+    double un = ws.at(Lm - 1, 9), xn[4] = {ws.at(Lm - 1, 5), ws.at(Lm - 1, 6), ws.at(Lm - 1, 7), ws.at(Lm - 1, 8)};
+    int sn = ws.state(Lm - 1);                              // (x, u, state) one stage ahead, as in box_backward
+    for (int t = Lm - 1; t >= 0; --t) {
+        const double* A = w.row(t);
+        const double f = A[21];
+        const double hi = tau - f, lo = -tau - f;
+        const double u = un;
+        const double x[4] = {xn[0], xn[1], xn[2], xn[3]};
+        const int s = sn;
+        const int tn = t > 0 ? t - 1 : 0;
+        un = ws.at(tn, 9);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xn[q] = ws.at(tn, 5 + q);
+        sn = ws.state(tn);
+        const double q = 2.0 * r * u + (((lam[0] * A[16] + lam[1] * A[17]) + lam[2] * A[18]) + lam[3] * A[19]);
+        const int ns = (u <= lo && q > 0.0) ? -1 : ((u >= hi && q < 0.0) ? 1 : 0);
+        changed |= ns != s;
+        ws.state(t) = ns;
+        ws.at(t, 5) = q;                                    // x_t is in registers; stage t - 1 is read already
+        double nl[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            nl[i] = 2.0 * (((Q.v[4 * i] * x[0] + Q.v[4 * i + 1] * x[1]) + Q.v[4 * i + 2] * x[2]) + Q.v[4 * i + 3] * x[3]) +
+                    (((A[i] * lam[0] + A[4 + i] * lam[1]) + A[8 + i] * lam[2]) + A[12 + i] * lam[3]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lam[i] = nl[i];
+    }
+    return changed;
+}
+
+// forward pass of box_backward's (k, d) along its own states: ubar_t -> slot 6; whether a free ubar_t is out of bounds
+__device__ __forceinline__ bool box_pn_target(const BoxWin& w, int Lm, const BoxWs& ws, double tau, double x0,
+                                              double x1, double x2, double x3) {
+    bool viol = false;
+    double kn[4], dn = ws.at(0, 4);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) kn[q] = ws.at(0, q);
+    int sn = ws.state(0);
+    for (int t = 0; t < Lm; ++t) {
+        const double* A = w.row(t);
+        const int s = sn;
+        const double k[4] = {kn[0], kn[1], kn[2], kn[3]};
+        const double d = dn;
+        const int tn = t + 1 < Lm ? t + 1 : t;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) kn[q] = ws.at(tn, q);
+        dn = ws.at(tn, 4);
+        sn = ws.state(tn);
+        const double u = s == 0 ? box_gain_dot(k, x0, x1, x2, x3) + d : d;
+        viol |= (s == 0) & ((u > tau - A[21]) | (u < -tau - A[21]));
+        ws.at(t, 6) = u;
+        const double n0 = (((A[0] * x0 + A[1] * x1) + A[2] * x2) + A[3] * x3) + A[16] * u;
+        const double n1 = (((A[4] * x0 + A[5] * x1) + A[6] * x2) + A[7] * x3) + A[17] * u;
+        const double n2 = (((A[8] * x0 + A[9] * x1) + A[10] * x2) + A[11] * x3) + A[18] * u;
+        const double n3 = (((A[12] * x0 + A[13] * x1) + A[14] * x2) + A[15] * x3) + A[19] * u;
+        x0 = n0; x1 = n1; x2 = n2; x3 = n3;
+    }
+    return viol;
+}
+
+// the step of one stage: v = u(a) = clip(u + a (ubar - u), lo, hi); a = 0 or a NaN target moves nothing
+__device__ __forceinline__ double box_pn_step(double u, double ub, double a, double lo, double hi) {
+    if (a == 0.0) return u;
+    const double c = u + a * (ub - u);
+    const double v = c > hi ? hi : (c < lo ? lo : c);
+    return v == v ? v : u;
+}
+
+// One trial of the search: the decrease J(u(a)) - J(u) = slope + quad, with slope = q'D the Armijo slope, D = u(a) - u
+// and quad = 1/2 D'H D the cost of the linear rollout of D from a zero state.  J is quadratic, so this is the
+// difference itself, without its cancellation: on a diverged closed loop J is 2e9 while the decrease of a last step
+// can be 0 exactly (every stage on its bound: nothing moves, and the step must be accepted), which a difference of
+// two separately rounded costs cannot resolve.
+__device__ __forceinline__ void box_pn_trial(const BoxWin& w, int Lm, const M44& Q, double r, const double* QT,
+                                             double tau, const BoxWs& ws, double a, double& slope, double& quad) {
+    double un = ws.at(0, 9), bn = ws.at(0, 6), qn = ws.at(0, 5);   // (u, ubar, q) one stage ahead
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0, cost = 0.0, sl = 0.0;
+    for (int t = 0; t < Lm; ++t) {
+        const double* A = w.row(t);
+        const double f = A[21];
+        const double u = un, ub = bn, q = qn;
+        const int tn = t + 1 < Lm ? t + 1 : t;
+        un = ws.at(tn, 9); bn = ws.at(tn, 6); qn = ws.at(tn, 5);
+        const double dl = box_pn_step(u, ub, a, -tau - f, tau - f) - u;
+        sl += q * dl;
+        const double x[4] = {x0, x1, x2, x3};
+        double xq = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            xq += x[i] * (((Q.v[4 * i] * x0 + Q.v[4 * i + 1] * x1) + Q.v[4 * i + 2] * x2) + Q.v[4 * i + 3] * x3);
+        cost += xq + (r * dl) * dl;
+        const double n0 = (((A[0] * x0 + A[1] * x1) + A[2] * x2) + A[3] * x3) + A[16] * dl;
+        const double n1 = (((A[4] * x0 + A[5] * x1) + A[6] * x2) + A[7] * x3) + A[17] * dl;
+        const double n2 = (((A[8] * x0 + A[9] * x1) + A[10] * x2) + A[11] * x3) + A[18] * dl;
+        const double n3 = (((A[12] * x0 + A[13] * x1) + A[14] * x2) + A[15] * x3) + A[19] * dl;
+        x0 = n0; x1 = n1; x2 = n2; x3 = n3;
+    }
+    const double x[4] = {x0, x1, x2, x3};
+    double xq = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        xq += x[i] * (((QT[4 * i] * x0 + QT[4 * i + 1] * x1) + QT[4 * i + 2] * x2) + QT[4 * i + 3] * x3);
+    slope = sl;
+    quad = cost + xq;
+}
+
+// the step taken: v = u(a) and its states from e -> x_t slots 5-8, v_t slot 9, x_{L-1}.  a = 0: v = u, nothing of
+// ubar or q enters the result (the slots may hold anything); this is also how a leaving lane gets its states back.
+__device__ __forceinline__ void box_pn_store(const BoxWin& w, int Lm, double tau, const BoxWs& ws, double a, double x0,
+                                             double x1, double x2, double x3, double& u_first) {
+    double un = ws.at(0, 9), bn = ws.at(0, 6);                     // (u, ubar) one stage ahead
+    for (int t = 0; t < Lm; ++t) {
+        const double* A = w.row(t);
+        const double f = A[21];
+        const double u = un, ub = bn;
+        const int tn = t + 1 < Lm ? t + 1 : t;
+        un = ws.at(tn, 9); bn = ws.at(tn, 6);
+        const double v = box_pn_step(u, ub, a, -tau - f, tau - f);
+        if (t == 0) u_first = v;
+        ws.at(t, 5) = x0; ws.at(t, 6) = x1; ws.at(t, 7) = x2; ws.at(t, 8) = x3;
+        ws.at(t, 9) = v;
+        const double n0 = (((A[0] * x0 + A[1] * x1) + A[2] * x2) + A[3] * x3) + A[16] * v;
+        const double n1 = (((A[4] * x0 + A[5] * x1) + A[6] * x2) + A[7] * x3) + A[17] * v;
+        const double n2 = (((A[8] * x0 + A[9] * x1) + A[10] * x2) + A[11] * x3) + A[18] * v;
+        const double n3 = (((A[12] * x0 + A[13] * x1) + A[14] * x2) + A[15] * x3) + A[19] * v;
+        x0 = n0; x1 = n1; x2 = n2; x3 = n3;
+    }
+    ws.at(Lm, 0) = x0; ws.at(Lm, 1) = x1; ws.at(Lm, 2) = x2; ws.at(Lm, 3) = x3;
+}
+
+// The second phase of one lane's QP, from the clipped iterate in slot 9 (feasible; x of slots 5-8 is the unclipped
+// iterate's and is not used).  Adds its Newton iterations (one Riccati sweep each) to iters.  The loop runs to a wave
+// vote, as box_qp_lane's does; lanes that are done (or did not enter) sit out.  Every exit leaves (x, u) of the
+// result in the workspace.
+__device__ __forceinline__ void box_pn_lane(const BoxWin& w, int Lm, const M44& Q, double r, const double* QT,
+                                            double tau, int fb_it, const BoxWs& ws, bool enter, double e0, double e1,
+                                            double e2, double e3, double& u_first, int& iters, bool& conv) {
+    bool active = enter, full = false;
+    double uf;
+    if (active) box_pn_store(w, Lm, tau, ws, 0.0, e0, e1, e2, e3, uf);
+    for (int n = 0; n <= fb_it; ++n) {
+        if (!__any(active)) break;
+        if (active) {
+            const bool changed = box_pn_gradient(w, Lm, Q, r, QT, tau, ws);
+            if (n > 0 && full && !changed) {
+                conv = true;
+                active = false;
+            } else if (n == fb_it) {
+                active = false;
+            } else {
+                iters += 1;
+                box_backward(w, Lm, Q, r, QT, tau, ws, false);
+                const bool viol = box_pn_target(w, Lm, ws, tau, e0, e1, e2, e3);
+                double a = 1.0, slope, quad;
+                bool took = false;
+                for (int j = 0; j < kBoxPnTrials; ++j) {
+                    box_pn_trial(w, Lm, Q, r, QT, tau, ws, a, slope, quad);
+                    if (slope + quad <= kBoxPnSigma * slope) { took = true; break; }
+                    a *= 0.5;
+                }
+                if (took) {
+                    box_pn_store(w, Lm, tau, ws, a, e0, e1, e2, e3, uf);
+                    full = a == 1.0 && !viol;
+                } else {
+                    active = false;                         // no step found: unconverged, returns u
+                }
+            }
+            // q overwrote slot 5: a lane that leaves here rolls its states out again
+            if (!active) box_pn_store(w, Lm, tau, ws, 0.0, e0, e1, e2, e3, u_first);
+        }
+    }
+}
+
 // One lane's QP from e = x0; u_first = u_0 of channel 1.  WS_RESULT: (x_t, u_t) of the result are always left in the
 // workspace (the batch kernel's outputs); without it a first iterate (shared gains) that violates no bound -- the
 // exact minimiser: no free stage changes state -- ends the QP after a forward pass that stores nothing.
 // The loop runs until every lane of the wavefront is done; lanes that are done (or not valid) sit out.
-template <bool WS_RESULT>
+// FALLBACK: a QP that reaches max_it goes on in box_pn_lane for at most fb_it Newton iterations (iters counts both
+// phases, so iters > max_it exactly when the fallback ran; conv: either phase finished); without it fb_it is not read.
+template <bool WS_RESULT, bool FALLBACK = false>
 __device__ __forceinline__ void box_qp_lane(const BoxWin& w, int Lm, const M44& Q, double r, const double* QT,
                                             double tau, int max_it, const BoxWs& ws, bool valid, double e0, double e1,
-                                            double e2, double e3, double& u_first, int& iters, bool& conv) {
+                                            double e2, double e3, double& u_first, int& iters, bool& conv,
+                                            int fb_it = 0) {
     bool active = valid;
     conv = false;
     iters = 0;
@@ -253,6 +460,8 @@ __device__ __forceinline__ void box_qp_lane(const BoxWin& w, int Lm, const M44& 
             if (t == 0) u_first = c;
         }
     }
+    if constexpr (FALLBACK)
+        box_pn_lane(w, Lm, Q, r, QT, tau, fb_it, ws, valid && !conv, e0, e1, e2, e3, u_first, iters, conv);
 }
 
 // the applied torque u_ref + u_0 of one channel: a first control on its bound is the limit itself (hi + u_ref is
@@ -294,104 +503,25 @@ __global__ __launch_bounds__(64) void k_mpc_box_stages(Dyn m, const double* __re
 
 constexpr int kBoxMaxLm = kMpcMaxStages - 3;   // L - 1 <= 253 stages per window (L + 2 <= 256)
 
-// A batch of QPs on one window: x0 (B,4) -> U (B,L-1,2), X (B,L,4), iterations and converged flag per QP
-__global__ __launch_bounds__(64) void k_mpc_box_qp(BoxTable tb, int L, M44 Q, double r, const double* __restrict__ QT,
-                                                   double tau, int max_it, const double* __restrict__ x0, int64_t B,
-                                                   double* wsd, int32_t* wst, int64_t Bp, double* __restrict__ U,
-                                                   double* __restrict__ X, int32_t* __restrict__ iters_out,
-                                                   int32_t* __restrict__ conv_out) {
-    __shared__ double rows[kBoxMaxLm * kBoxRow];
-    const int ln = threadIdx.x;
-    const int64_t l = (int64_t)blockIdx.x * blockDim.x + ln;
-    const bool valid = l < B;
-    const int Lm = L - 1;
-    for (int idx = ln; idx < Lm * kBoxRow; idx += 64) rows[idx] = box_row_elem(tb, idx / kBoxRow, idx % kBoxRow);
-    wave_lds_order();
-    const BoxWin w{rows, nullptr, 0, Lm};
-    const BoxWs ws{wsd, wst, Bp, l};
-    const int64_t lr = valid ? l : 0;
-    double u_first;
-    int iters;
-    bool conv;
-    box_qp_lane<true>(w, Lm, Q, r, QT, tau, max_it, ws, valid, x0[4 * lr], x0[4 * lr + 1], x0[4 * lr + 2],
-                      x0[4 * lr + 3], u_first, iters, conv);
-    if (!valid) return;
-    double* Ul = U + 2 * (int64_t)Lm * l;
-    double* Xl = X + 4 * (int64_t)L * l;
-    for (int t = 0; t < Lm; ++t) {
-        Ul[2 * t] = box_clip0(w.row(t)[20], tau);
-        Ul[2 * t + 1] = ws.at(t, 9);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Xl[4 * t + q] = ws.at(t, 5 + q);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) Xl[4 * Lm + q] = ws.at(Lm, q);
-    iters_out[l] = iters;
-    conv_out[l] = conv ? 1 : 0;
-}
-
-// The torque-limited closed loop (solve_mpc_tracking :43-67), one trajectory per lane.  Per control step s: e = x -
-// x_ref[s], the window's QP (rows s .. s+L-2 of the stage table, the pad past its end; first iterate from K_all's
-// window s), u_real[s] = u_ref[s] + u_0, one RK4 step.  Lane-major x (B,N,4), u (B,N-1,2), qp_iters (B,N-1) and the
-// lane's count of unconverged QPs.  The wavefront keeps the window's rows in an LDS ring (one new row per step) and
-// loads the window's Kw (row 1 of each gain) at the top of the step.
-__global__ __launch_bounds__(64) void k_mpc_box_rollout(Dyn m, BoxTable tb, int L, M44 Q, double r,
-                                                        const double* __restrict__ QT, double tau, int max_it,
-                                                        const double* __restrict__ x0,
-                                                        const double* __restrict__ x_ref,
-                                                        const double* __restrict__ K_all, int64_t B, int N,
-                                                        double* wsd, int32_t* wst, int64_t Bp,
-                                                        double* __restrict__ xo, double* __restrict__ uo,
-                                                        int32_t* __restrict__ it_out, int32_t* __restrict__ unconv_out) {
-    __shared__ double rows[kBoxMaxLm * kBoxRow];
-    __shared__ double kw[kBoxMaxLm * 4];
-    const int ln = threadIdx.x;
-    const int64_t l = (int64_t)blockIdx.x * blockDim.x + ln;
-    const bool valid = l < B;
-    const int64_t lr = valid ? l : 0;
-    const int T = N - 1, Lm = L - 1;
-    const BoxWs ws{wsd, wst, Bp, l};
-    double2* xl = reinterpret_cast<double2*>(xo + 4 * (int64_t)N * lr);
-    double2* ul = reinterpret_cast<double2*>(uo + 2 * (int64_t)T * lr);
-    int32_t* il = it_out + (int64_t)T * lr;
-    double n0 = x0[4 * lr], n1 = x0[4 * lr + 1], n2 = x0[4 * lr + 2], n3 = x0[4 * lr + 3];
-    if (valid) {
-        xl[0] = make_double2(n0, n1);
-        xl[1] = make_double2(n2, n3);
-    }
-    const gym::PolyRegs pk = gym::poly_vgprs();
-    int unconv = 0;
-    BoxWin w{rows, kw, 0, Lm};
-    for (int s = 0; s < T; ++s) {
-        wave_lds_order();                               // the previous step's LDS reads are done
-        if (s == 0) {
-            for (int idx = ln; idx < Lm * kBoxRow; idx += 64) rows[idx] = box_row_elem(tb, idx / kBoxRow, idx % kBoxRow);
-        } else {                                        // stage s + Lm - 1 replaces stage s - 1 in the ring
-            if (ln < kBoxRow) rows[kBoxRow * w.base + ln] = box_row_elem(tb, s + Lm - 1, ln);
-            w.base = w.base + 1 == Lm ? 0 : w.base + 1;
-        }
-        const double* Ks = K_all + 8 * (int64_t)s * Lm;
-        for (int idx = ln; idx < 4 * Lm; idx += 64) kw[idx] = Ks[8 * (idx >> 2) + 4 + (idx & 3)];
-        wave_lds_order();
-        const double* r4 = x_ref + 4 * (int64_t)s;
-        const double* f = w.row(0) + 20;                // u_ref[s]
-        double u1;
-        int iters;
-        bool conv;
-        box_qp_lane<false>(w, Lm, Q, r, QT, tau, max_it, ws, valid, n0 - r4[0], n1 - r4[1], n2 - r4[2], n3 - r4[3], u1,
-                           iters, conv);
-        if (valid) {
-            const double v0 = box_apply(f[0], box_clip0(f[0], tau), tau), v1 = box_apply(f[1], u1, tau);
-            ul[s] = make_double2(v0, v1);
-            il[s] = iters;
-            unconv += conv ? 0 : 1;
-            gym::rk4(m, n0, n1, n2, n3, v1, pk);
-            xl[2 * (s + 1)] = make_double2(n0, n1);
-            xl[2 * (s + 1) + 1] = make_double2(n2, n3);
-        }
-    }
-    if (valid) unconv_out[l] = unconv;
-}
+// k_mpc_box_qp, k_mpc_box_rollout and their fallback twins k_mpc_box_qp_fb, k_mpc_box_rollout_fb: one text, two passes
+#define GYM_BOX_K(name) name
+#define GYM_BOX_FB false
+#define GYM_BOX_FB_PARAM
+#define GYM_BOX_FB_ARG
+#include "mpc_box_kernels.def.hpp"
+#undef GYM_BOX_K
+#undef GYM_BOX_FB
+#undef GYM_BOX_FB_PARAM
+#undef GYM_BOX_FB_ARG
+#define GYM_BOX_K(name) name##_fb
+#define GYM_BOX_FB true
+#define GYM_BOX_FB_PARAM int fb_it,
+#define GYM_BOX_FB_ARG , fb_it
+#include "mpc_box_kernels.def.hpp"
+#undef GYM_BOX_K
+#undef GYM_BOX_FB
+#undef GYM_BOX_FB_PARAM
+#undef GYM_BOX_FB_ARG
 
 // workspace of B lanes, windows of L stages, a stage table of `rows` rows: table, then per-lane doubles, then states
 struct BoxLayout {

@@ -151,10 +151,11 @@ int gym_mpc_box_workspace(int64_t B, int32_t L, int32_t rows, int64_t* bytes_out
     return 0;
 }
 
-int gym_mpc_box_qp(const double* A, const double* Bm, const double* u_ref, int32_t S, const double Q[16],
-                   const double R[4], const double* QT, const double* x0, int64_t B, int32_t L, double tau_max,
-                   int32_t max_qp_iters, void* ws, int64_t ws_bytes, double* U, double* X, int32_t* iters_out,
-                   int32_t* converged_out, void* s) {
+// fallback_iters = 0: the active set alone (k_mpc_box_qp); >= 1: with the projected-Newton fallback (k_mpc_box_qp_fb)
+static int box_qp_launch(const double* A, const double* Bm, const double* u_ref, int32_t S, const double Q[16],
+                         const double R[4], const double* QT, const double* x0, int64_t B, int32_t L, double tau_max,
+                         int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes, double* U, double* X,
+                         int32_t* iters_out, int32_t* converged_out, void* s) {
     if (!A || !Bm || !u_ref || !Q || !R || !QT || !x0 || !ws || !U || !X || !iters_out || !converged_out ||
         !box_sizes_ok(B, L, tau_max, max_qp_iters) || S < L - 1 || !box_weights_ok(R))
         return GYM_EINVAL;
@@ -167,17 +168,39 @@ int gym_mpc_box_qp(const double* A, const double* Bm, const double* u_ref, int32
     if (e == hipSuccess) e = hipMemcpyAsync(w.Bm, Bm, 8 * sizeof(double) * S, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(w.ur, u_ref, 2 * sizeof(double) * S, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_mpc_box_qp, dim3((unsigned)(w.lo.Bp / 64)), dim3(64), 0, st, BoxTable{w.A, w.Bm, w.ur, S - 1},
-                       L, m44(Q), R[3], QT, tau_max, max_qp_iters, x0, B, w.d, w.st, w.lo.Bp, U, X, iters_out,
-                       converged_out);
+    const dim3 grid((unsigned)(w.lo.Bp / 64));
+    const BoxTable tb{w.A, w.Bm, w.ur, S - 1};
+    if (fallback_iters)
+        hipLaunchKernelGGL(k_mpc_box_qp_fb, grid, dim3(64), 0, st, tb, L, m44(Q), R[3], QT, tau_max, max_qp_iters,
+                           fallback_iters, x0, B, w.d, w.st, w.lo.Bp, U, X, iters_out, converged_out);
+    else
+        hipLaunchKernelGGL(k_mpc_box_qp, grid, dim3(64), 0, st, tb, L, m44(Q), R[3], QT, tau_max, max_qp_iters, x0, B,
+                           w.d, w.st, w.lo.Bp, U, X, iters_out, converged_out);
     return launch_status();
 }
 
-int gym_mpc_box_rollout(const gym_model* m, const double* x0, const double* x_ref, const double* u_ref,
-                        const double* x_f, const double* u_f, const double Q[16], const double R[4], const double* QT,
-                        const double* K_all, int64_t B, int32_t N, int32_t L, double tau_max, int32_t max_qp_iters,
-                        void* ws, int64_t ws_bytes, double* x_out, double* u_out, int32_t* qp_iters_out,
-                        int32_t* unconverged_out, void* s) {
+int gym_mpc_box_qp(const double* A, const double* Bm, const double* u_ref, int32_t S, const double Q[16],
+                   const double R[4], const double* QT, const double* x0, int64_t B, int32_t L, double tau_max,
+                   int32_t max_qp_iters, void* ws, int64_t ws_bytes, double* U, double* X, int32_t* iters_out,
+                   int32_t* converged_out, void* s) {
+    return box_qp_launch(A, Bm, u_ref, S, Q, R, QT, x0, B, L, tau_max, max_qp_iters, 0, ws, ws_bytes, U, X, iters_out,
+                         converged_out, s);
+}
+
+int gym_mpc_box_qp_fallback(const double* A, const double* Bm, const double* u_ref, int32_t S, const double Q[16],
+                            const double R[4], const double* QT, const double* x0, int64_t B, int32_t L,
+                            double tau_max, int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes,
+                            double* U, double* X, int32_t* iters_out, int32_t* converged_out, void* s) {
+    if (fallback_iters < 1) return GYM_EINVAL;
+    return box_qp_launch(A, Bm, u_ref, S, Q, R, QT, x0, B, L, tau_max, max_qp_iters, fallback_iters, ws, ws_bytes, U,
+                         X, iters_out, converged_out, s);
+}
+
+static int box_rollout_launch(const gym_model* m, const double* x0, const double* x_ref, const double* u_ref,
+                              const double* x_f, const double* u_f, const double Q[16], const double R[4],
+                              const double* QT, const double* K_all, int64_t B, int32_t N, int32_t L, double tau_max,
+                              int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes, double* x_out,
+                              double* u_out, int32_t* qp_iters_out, int32_t* unconverged_out, void* s) {
     if (!m || !x0 || !x_ref || !u_ref || !x_f || !u_f || !Q || !R || !QT || !K_all || !ws || !x_out || !u_out ||
         !qp_iters_out || !unconverged_out || !box_sizes_ok(B, L, tau_max, max_qp_iters) || N < 2 ||
         !box_weights_ok(R))
@@ -188,10 +211,37 @@ int gym_mpc_box_rollout(const gym_model* m, const double* x0, const double* x_re
     hipStream_t st = (hipStream_t)s;
     hipLaunchKernelGGL(k_mpc_box_stages, dim3((unsigned)((S + 1 + 63) / 64)), dim3(64), 0, st, Dyn(*m), x_ref, u_ref,
                        S, x_f, u_f, w.A, w.Bm, w.ur);
-    hipLaunchKernelGGL(k_mpc_box_rollout, dim3((unsigned)(w.lo.Bp / 64)), dim3(64), 0, st, Dyn(*m),
-                       BoxTable{w.A, w.Bm, w.ur, S}, L, m44(Q), R[3], QT, tau_max, max_qp_iters, x0, x_ref, K_all, B, N,
-                       w.d, w.st, w.lo.Bp, x_out, u_out, qp_iters_out, unconverged_out);
+    const dim3 grid((unsigned)(w.lo.Bp / 64));
+    const BoxTable tb{w.A, w.Bm, w.ur, S};
+    if (fallback_iters)
+        hipLaunchKernelGGL(k_mpc_box_rollout_fb, grid, dim3(64), 0, st, Dyn(*m), tb, L, m44(Q), R[3], QT, tau_max,
+                           max_qp_iters, fallback_iters, x0, x_ref, K_all, B, N, w.d, w.st, w.lo.Bp, x_out, u_out,
+                           qp_iters_out, unconverged_out);
+    else
+        hipLaunchKernelGGL(k_mpc_box_rollout, grid, dim3(64), 0, st, Dyn(*m), tb, L, m44(Q), R[3], QT, tau_max,
+                           max_qp_iters, x0, x_ref, K_all, B, N, w.d, w.st, w.lo.Bp, x_out, u_out, qp_iters_out,
+                           unconverged_out);
     return launch_status();
+}
+
+int gym_mpc_box_rollout(const gym_model* m, const double* x0, const double* x_ref, const double* u_ref,
+                        const double* x_f, const double* u_f, const double Q[16], const double R[4], const double* QT,
+                        const double* K_all, int64_t B, int32_t N, int32_t L, double tau_max, int32_t max_qp_iters,
+                        void* ws, int64_t ws_bytes, double* x_out, double* u_out, int32_t* qp_iters_out,
+                        int32_t* unconverged_out, void* s) {
+    return box_rollout_launch(m, x0, x_ref, u_ref, x_f, u_f, Q, R, QT, K_all, B, N, L, tau_max, max_qp_iters, 0, ws,
+                              ws_bytes, x_out, u_out, qp_iters_out, unconverged_out, s);
+}
+
+int gym_mpc_box_rollout_fallback(const gym_model* m, const double* x0, const double* x_ref, const double* u_ref,
+                                 const double* x_f, const double* u_f, const double Q[16], const double R[4],
+                                 const double* QT, const double* K_all, int64_t B, int32_t N, int32_t L,
+                                 double tau_max, int32_t max_qp_iters, int32_t fallback_iters, void* ws,
+                                 int64_t ws_bytes, double* x_out, double* u_out, int32_t* qp_iters_out,
+                                 int32_t* unconverged_out, void* s) {
+    if (fallback_iters < 1) return GYM_EINVAL;
+    return box_rollout_launch(m, x0, x_ref, u_ref, x_f, u_f, Q, R, QT, K_all, B, N, L, tau_max, max_qp_iters,
+                              fallback_iters, ws, ws_bytes, x_out, u_out, qp_iters_out, unconverged_out, s);
 }
 
 int gym_lq_forward(const double* A, const double* Bm, int32_t S, const double* A_pad, const double* B_pad,
@@ -288,11 +338,11 @@ int gym_mpc_box_lanes_workspace(int64_t B, int32_t P, int32_t L, int64_t* bytes_
 }
 
 // solve_mpc_tracking's closed loop (trajectory_tracking.py:43-67) with solver_mpc's test_constraints (:87-114) per lane
-int gym_mpc_box_lanes_rollout(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0, int64_t B,
-                              int32_t P, int32_t N, int32_t L, const double Q[16], const double R[4],
-                              const double* QT_dev, double tau_max, int32_t max_qp_iters, void* ws, int64_t ws_bytes,
-                              double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
-                              int32_t* unconverged_out, void* s) {
+static int box_lanes_launch(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0, int64_t B,
+                            int32_t P, int32_t N, int32_t L, const double Q[16], const double R[4],
+                            const double* QT_dev, double tau_max, int32_t max_qp_iters, int32_t fallback_iters,
+                            void* ws, int64_t ws_bytes, double* x_out, double* u_out, double* summary_out,
+                            int32_t* qp_iters_out, int32_t* unconverged_out, void* s) {
     if (!m || !x_opt || !u_opt || !x0 || !Q || !R || !QT_dev || !ws || !summary_out || !unconverged_out ||
         !box_lanes_sizes_ok(B, P, N, L) || !finite_pos(tau_max) || max_qp_iters < 1 || !box_weights_ok(R) ||
         !lanes_sym(Q) || (x_out == nullptr) != (u_out == nullptr))
@@ -301,12 +351,39 @@ int gym_mpc_box_lanes_rollout(const gym_model* m, const double* x_opt, const dou
     if (ws_bytes < lo.bytes) return GYM_EINVAL;
     const int nblk = (P + 63) / 64;                        // B nblk <= B P <= GYM_MAX_BP: far below the grid limit
     const size_t lds = sizeof(double) * (kBoxRow + 4) * (L - 1);
-    hipLaunchKernelGGL(k_mpc_box_lane_rollout, dim3((unsigned)(B * nblk)), dim3(64), lds, (hipStream_t)s, Dyn(*m),
-                       m44(Q), R[3], QT_dev, tau_max, max_qp_iters, reinterpret_cast<const double2*>(x_opt),
-                       reinterpret_cast<const double2*>(u_opt), x0, (int)P, (int)N, (int)L, nblk,
-                       ws_at<double>(ws, 0), ws_at<int32_t>(ws, lo.off_st), x_out, u_out, summary_out, qp_iters_out,
-                       unconverged_out);
+    const dim3 grid((unsigned)(B * nblk));
+    const double2* xo2 = reinterpret_cast<const double2*>(x_opt);
+    const double2* uo2 = reinterpret_cast<const double2*>(u_opt);
+    if (fallback_iters)
+        hipLaunchKernelGGL(k_mpc_box_lane_rollout_fb, grid, dim3(64), lds, (hipStream_t)s, Dyn(*m), m44(Q), R[3],
+                           QT_dev, tau_max, max_qp_iters, fallback_iters, xo2, uo2, x0, (int)P, (int)N, (int)L, nblk,
+                           ws_at<double>(ws, 0), ws_at<int32_t>(ws, lo.off_st), x_out, u_out, summary_out,
+                           qp_iters_out, unconverged_out);
+    else
+        hipLaunchKernelGGL(k_mpc_box_lane_rollout, grid, dim3(64), lds, (hipStream_t)s, Dyn(*m), m44(Q), R[3], QT_dev,
+                           tau_max, max_qp_iters, xo2, uo2, x0, (int)P, (int)N, (int)L, nblk, ws_at<double>(ws, 0),
+                           ws_at<int32_t>(ws, lo.off_st), x_out, u_out, summary_out, qp_iters_out, unconverged_out);
     return launch_status();
+}
+
+int gym_mpc_box_lanes_rollout(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0, int64_t B,
+                              int32_t P, int32_t N, int32_t L, const double Q[16], const double R[4],
+                              const double* QT_dev, double tau_max, int32_t max_qp_iters, void* ws, int64_t ws_bytes,
+                              double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
+                              int32_t* unconverged_out, void* s) {
+    return box_lanes_launch(m, x_opt, u_opt, x0, B, P, N, L, Q, R, QT_dev, tau_max, max_qp_iters, 0, ws, ws_bytes,
+                            x_out, u_out, summary_out, qp_iters_out, unconverged_out, s);
+}
+
+int gym_mpc_box_lanes_rollout_fallback(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0,
+                                       int64_t B, int32_t P, int32_t N, int32_t L, const double Q[16],
+                                       const double R[4], const double* QT_dev, double tau_max, int32_t max_qp_iters,
+                                       int32_t fallback_iters, void* ws, int64_t ws_bytes, double* x_out,
+                                       double* u_out, double* summary_out, int32_t* qp_iters_out,
+                                       int32_t* unconverged_out, void* s) {
+    if (fallback_iters < 1) return GYM_EINVAL;
+    return box_lanes_launch(m, x_opt, u_opt, x0, B, P, N, L, Q, R, QT_dev, tau_max, max_qp_iters, fallback_iters, ws,
+                            ws_bytes, x_out, u_out, summary_out, qp_iters_out, unconverged_out, s);
 }
 
 }  // extern "C"

@@ -446,10 +446,14 @@ class AcrobotEngine:
         """The caller-owned workspace of gym_mpc_box_qp (rows = stages given) / gym_mpc_box_rollout (rows = N)."""
         return self._workspace(None, "gym_mpc_box_workspace", B, L, rows)[0]
 
-    def mpc_box_qp(self, A, Bm, u_ref, Q, R, QT, x0, L: int, tau_max: float, max_qp_iters: int = 32, ws=None):
+    def mpc_box_qp(self, A, Bm, u_ref, Q, R, QT, x0, L: int, tau_max: float, max_qp_iters: int = 32, ws=None,
+                   fallback_iters: int = 0):
         """gym_mpc_box_qp: the torque-limited QP of one window for a batch x0 (B,4).  Stages A (S,4,4), Bm (S,4,2),
         u_ref (S,2) are host arrays (S >= L-1).  Returns device tensors U (B,L-1,2), X (B,L,4), iterations (B,)
-        int32, converged (B,) int32."""
+        int32, converged (B,) int32.  ``fallback_iters`` > 0 (gym_mpc_box_qp_fallback): a QP at the cap goes on by
+        projected Newton for at most that many iterations; iterations then counts both phases (> max_qp_iters
+        exactly when the fallback ran) and converged is false only where neither phase finished."""
+        fb = check_fallback(fallback_iters)
         A = np.ascontiguousarray(np.asarray(A, dtype=np.float64)).reshape(-1, 4, 4)
         Bm = np.ascontiguousarray(np.asarray(Bm, dtype=np.float64)).reshape(-1, 4, 2)
         ur = np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64)).reshape(-1, 2)
@@ -467,14 +471,17 @@ class AcrobotEngine:
         ws, ws_bytes = self._workspace(ws, "gym_mpc_box_workspace", B, L, S)
         U, X = self._buf(B, L - 1, 2), self._buf(B, L, 4)
         it, conv = self._buf(B, dtype=I32), self._buf(B, dtype=I32)
-        self._call("gym_mpc_box_qp", A, Bm, ur, S, Qh, Rh, QTd, x0, B, L, float(tau_max), int(max_qp_iters), ws,
-                   ws_bytes, U, X, it, conv)
+        self._call(*_with_fallback("gym_mpc_box_qp", fb, A, Bm, ur, S, Qh, Rh, QTd, x0, B, L, float(tau_max),
+                                   int(max_qp_iters)), ws, ws_bytes, U, X, it, conv)
         return U, X, it, conv
 
     def mpc_box_rollout(self, x0, x_ref, u_ref, x_f, u_f, Q, R, QT, K_all, tau_max: float, max_qp_iters: int = 32,
-                        ws=None):
+                        ws=None, fallback_iters: int = 0):
         """gym_mpc_box_rollout: the torque-limited closed loop of B lanes.  Returns device tensors x (B,N,4),
-        u (B,N-1,2), qp_iters (B,N-1) int32, unconverged (B,) int32."""
+        u (B,N-1,2), qp_iters (B,N-1) int32, unconverged (B,) int32.  ``fallback_iters`` > 0
+        (gym_mpc_box_rollout_fallback): qp_iters counts active-set sweeps plus Newton iterations and unconverged only
+        the QPs that neither phase finished."""
+        fb = check_fallback(fallback_iters)
         x0 = self.t(x0).reshape(-1, 4)
         x_ref = self.t(x_ref).reshape(-1, 4); u_ref = self.t(u_ref).reshape(-1, 2)
         x_f = self.t(x_f).reshape(4); u_f = self.t(u_f).reshape(2)
@@ -491,8 +498,8 @@ class AcrobotEngine:
         ws, ws_bytes = self._workspace(ws, "gym_mpc_box_workspace", B, L, N)
         x, u = self._buf(B, N, 4), self._buf(B, N - 1, 2)
         it, unconv = self._buf(B, N - 1, dtype=I32), self._buf(B, dtype=I32)
-        self._call("gym_mpc_box_rollout", self.model, x0, x_ref, u_ref, x_f, u_f, Qh, Rh, QTd, K_all, B, N, L,
-                   float(tau_max), int(max_qp_iters), ws, ws_bytes, x, u, it, unconv)
+        self._call(*_with_fallback("gym_mpc_box_rollout", fb, self.model, x0, x_ref, u_ref, x_f, u_f, Qh, Rh, QTd,
+                                   K_all, B, N, L, float(tau_max), int(max_qp_iters)), ws, ws_bytes, x, u, it, unconv)
         return x, u, it, unconv
 
     # ------------------------------------------------------------- per-lane LQR tracking
@@ -549,20 +556,23 @@ class AcrobotEngine:
         return self._ws_bytes("gym_mpc_box_lanes_workspace", B, P, L)
 
     def mpc_box_lanes_rollout(self, x_opt, u_opt, x0, Q, R, QT, L: int, tau_max: float, max_qp_iters: int = 32,
-                              trajectories: bool = True, max_ws_bytes: int | None = None):
+                              trajectories: bool = True, max_ws_bytes: int | None = None, fallback_iters: int = 0):
         """gym_mpc_box_lanes_rollout: the torque-limited MPC closed loop of every lane along its own x_opt (B,N,4),
         u_opt (B,N-1,2) from the starts x0 (B,P,4); QT (4,4) a device tensor as in mpc_lanes_gains.  Returns device
         tensors (x (B,P,N,4), u (B,P,N-1,2), summary (3,B,P), qp_iters (B,P,N-1) int32, unconverged (B,P) int32); x, u
         and qp_iters are None unless ``trajectories``.  The sweep workspace (about 80 (L-1) bytes per lane and start) is
         allocated here; a batch whose workspace would exceed ``max_ws_bytes`` (default: BOX_LANES_WS_SHARE of the free
-        device memory) runs in chunks of whole lanes, one call each -- the same results, lanes being independent."""
+        device memory) runs in chunks of whole lanes, one call each -- the same results, lanes being independent.
+        ``fallback_iters`` > 0 (gym_mpc_box_lanes_rollout_fallback, every chunk): qp_iters counts active-set sweeps
+        plus Newton iterations and unconverged only the QPs that neither phase finished."""
         x_opt = self.t(x_opt); u_opt = self.t(u_opt); x0 = self.t(x0)
         B, N = check_lane_trajectories(x_opt, u_opt)
         check_lane_starts(x0, B)
         P, L = x0.shape[1], check_window(L, "the torque-limited QP")
         if B * P > _lib.MAX_BP:
             raise ValueError(f"{B} lanes x {P} starts exceed {_lib.MAX_BP} closed loops per call")
-        check_box(tau_max, max_qp_iters)
+        check_box(tau_max, max_qp_iters, fallback_iters)
+        fb = int(fallback_iters)
         Rh = check_diagonal_R(R, "the torque-limited QP")
         Qh = check_sym_weight(Q, "Q")
         QTd = check_device_QT(self.t(QT))
@@ -578,9 +588,9 @@ class AcrobotEngine:
             b1 = min(B, b0 + chunk)
             part = lambda a: None if a is None else a[b0:b1]  # noqa: E731 -- this chunk's lanes of a lane-major buffer
             sm = summary if chunk >= B else self._buf(3, b1 - b0, P)
-            self._call("gym_mpc_box_lanes_rollout", self.model, part(x_opt), part(u_opt), part(x0), b1 - b0, P, N, L,
-                       Qh, Rh, QTd, float(tau_max), int(max_qp_iters), ws, ws.numel(), part(x), part(u), sm, part(it),
-                       part(unconv))
+            self._call(*_with_fallback("gym_mpc_box_lanes_rollout", fb, self.model, part(x_opt), part(u_opt), part(x0),
+                                       b1 - b0, P, N, L, Qh, Rh, QTd, float(tau_max), int(max_qp_iters)),
+                       ws, ws.numel(), part(x), part(u), sm, part(it), part(unconv))
             if sm is not summary:
                 summary[:, b0:b1] = sm
         return x, u, summary, it, unconv
@@ -672,12 +682,27 @@ def check_window(T_pred, what: str) -> int:
     return L
 
 
-def check_box(tau_max, max_qp_iters):
-    """The torque limit and the active set's sweep cap."""
+def check_box(tau_max, max_qp_iters, fallback_iters=0):
+    """The torque limit, the active set's sweep cap and the fallback's iteration cap (0: no fallback)."""
     if not (np.isfinite(tau_max) and tau_max > 0):
         raise ValueError(f"tau_max must be finite and positive, got {tau_max}")
     if int(max_qp_iters) < 1:
         raise ValueError(f"max_qp_iters must be at least 1, got {max_qp_iters}")
+    check_fallback(fallback_iters)
+
+
+def check_fallback(fallback_iters) -> int:
+    """The projected-Newton fallback's iteration cap, returned as an int: a whole number, 0 = off."""
+    fb = int(fallback_iters)
+    if fb != fallback_iters or fb < 0 or fb > 2 ** 31 - 1:
+        raise ValueError(f"fallback_iters must be a whole number in [0, 2^31), got {fallback_iters}")
+    return fb
+
+
+def _with_fallback(name, fb, *head):
+    """The call list up to max_qp_iters: the entry point itself, or with fb > 0 its ..._fallback twin, which takes
+    fallback_iters right after max_qp_iters."""
+    return (name + "_fallback",) + head + (fb,) if fb else (name,) + head
 
 
 def check_device_QT(QT):

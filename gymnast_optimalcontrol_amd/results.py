@@ -80,7 +80,10 @@ class SolveResult:
         """Receding-horizon MPC tracking of every lane's own result (trajectory_tracking.MPC_tracking_lanes on this
         result's x, u); x0 / dx0 as track_lqr.  Keyword arguments (T_pred, Q, R, trajectories, gains, tau_max,
         max_qp_iters) go to MPC_tracking_lanes.  Returns its MpcLanesResult; with a torque limit (``tau_max=18`` is the
-        reference's) every lane's closed loop keeps |u| <= tau_max and the result is an MpcBoxLanesResult."""
+        reference's) every lane's closed loop keeps |u| <= tau_max and the result is an MpcBoxLanesResult.
+        ``tau_max=trajectory_tracking.TorqueLimit(18.0)`` adds the projected-Newton fallback: a QP whose active set
+        has not settled after max_qp_iters sweeps is finished by it, qp_iters counts both phases and unconverged only
+        the QPs that neither phase finished."""
         from . import trajectory_tracking as tt
         return tt.MPC_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
 

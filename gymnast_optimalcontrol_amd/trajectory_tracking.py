@@ -16,7 +16,9 @@ With ``tau_max`` (the reference's test_constraints path, :87-114, tau_max = 18) 
 -tau_max <= u_t + u_ref_t <= tau_max, and each lane at each control step owns an inequality-constrained QP.  It
 is solved exactly by a primal-dual active set over a clamped Riccati sweep (gym_mpc_box_qp /
 gym_mpc_box_rollout; DESIGN "Torque-limited MPC"), at most ``max_qp_iters`` sweeps per QP; a QP that has not
-settled by then returns the clipped last iterate and is counted in ``unconverged``.
+settled by then returns the clipped last iterate and is counted in ``unconverged``.  ``tau_max=TorqueLimit(18.0)``
+turns the fallback on: such a QP goes on by projected Newton from that clipped iterate ("The fallback"),
+``qp_iters`` counts both phases and ``unconverged`` only the QPs that neither phase finished.
 
 Batched additions: ``LQR_tracking_batch``, ``solve_mpc_tracking_batch`` and ``solve_mpc_tracking_box_batch``
 take x0 (B,4) and return device tensors; they follow one reference shared by every lane.  ``LQR_tracking_lanes`` /
@@ -51,6 +53,32 @@ U_F = np.array([0.0, 0.0])                          # :32
 T_PRED = 75                                         # :10
 TAU_MAX = 18.0                                      # :91 (solver_mpc's torque limit, test_constraints)
 MPC_FUSED_MAX_STAGES = _lib.MPC_MAX_STAGES          # gym_mpc_gains: T_pred + 2 stages per workgroup's LDS table
+
+
+@dataclass(frozen=True)
+class TorqueLimit:
+    """A torque limit with the projected-Newton fallback, accepted wherever ``tau_max=`` is (solver_mpc,
+    solve_mpc_tracking, solve_mpc_tracking_box_batch, MPC_tracking_lanes, SolveResult.track_mpc).  A plain number
+    keeps its meaning: the active set alone, a QP that reaches ``max_qp_iters`` is clipped and counted unconverged.
+    With a TorqueLimit such a QP is continued by projected Newton from that clipped iterate for at most
+    ``fallback_iters`` iterations (one Riccati sweep each).  Then qp_iters = active-set sweeps + Newton iterations
+    (> max_qp_iters exactly when the fallback ran) and unconverged counts only QPs that neither phase finished.  QPs
+    that settle within max_qp_iters are the plain number's QPs bit for bit.  128 is a cap, about twice the largest
+    count seen on the CPU (69), not a tuned value; 0 is the plain number."""
+    tau_max: float
+    fallback_iters: int = 128
+
+
+def _torque_limit(tau_max):
+    """(tau_max, fallback_iters) of a ``tau_max=`` value: a number (no fallback), a TorqueLimit, or None."""
+    if isinstance(tau_max, TorqueLimit):
+        return tau_max.tau_max, tau_max.fallback_iters
+    return tau_max, 0
+
+
+def _fb_kw(fb) -> dict:
+    """The engine keyword of the fallback; none without it, so a plain tau_max makes the call it always made."""
+    return {"fallback_iters": int(fb)} if fb else {}
 
 
 def _eng():
@@ -252,7 +280,9 @@ class MpcBoxLanesResult(MpcLanesResult):
     """MPC_tracking_lanes' result with a torque limit: MpcLanesResult's fields (K = the windows' unconstrained first
     gains, the first iterate of every QP), unconverged (B,P) int32 = the QPs of that closed loop that reached
     ``max_qp_iters`` without settling (their clipped last iterate was applied), and qp_iters (B,P,N-1) int32
-    active-set sweeps per QP (None with ``trajectories=False``).  An x0 of shape (B,4) drops the P axis of both."""
+    active-set sweeps per QP (None with ``trajectories=False``).  An x0 of shape (B,4) drops the P axis of both.
+    With ``tau_max=TorqueLimit(...)``: qp_iters = active-set sweeps + Newton iterations of the fallback
+    (> max_qp_iters exactly when it ran), unconverged = the QPs that neither phase finished."""
     unconverged: torch.Tensor
     qp_iters: torch.Tensor | None
 
@@ -269,9 +299,11 @@ def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bo
     of every closed loop owns an inequality-constrained QP, solved by the active set of the shared-reference path
     (at most ``max_qp_iters`` sweeps each) in the kernel of csrc/mpc_box_lanes.hpp (gym_mpc_box_lanes_rollout; DESIGN
     4.7).  Returns an MpcBoxLanesResult then; where no bound is ever active its x, u and summaries are the
-    unlimited call's bit for bit."""
+    unlimited call's bit for bit.  ``tau_max=TorqueLimit(18.0)`` adds the projected-Newton fallback to every QP:
+    qp_iters then counts both phases and unconverged only the QPs that neither phase finished."""
+    tau_max, fb = _torque_limit(tau_max)
     if tau_max is not None:
-        _check_box(tau_max, T_pred, max_qp_iters)
+        _check_box(tau_max, T_pred, max_qp_iters, fb)
     eng = _eng()
     x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
     x0, flat = _lane_starts(eng, x0, x_opt)
@@ -282,7 +314,7 @@ def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bo
         return MpcLanesResult(x, u, K, s[0], s[1], s[2], QT.clone())
     K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=True)[1] if gains else None
     x, u, s, it, unconv = eng.mpc_box_lanes_rollout(x_opt, u_opt, x0, Q, R, QT, int(T_pred), float(tau_max),
-                                                    int(max_qp_iters), trajectories=trajectories)
+                                                    int(max_qp_iters), trajectories=trajectories, **_fb_kw(fb))
     s, x, u, it, unconv = _drop_starts_axis(flat, s, x, u, it, unconv)
     return MpcBoxLanesResult(x, u, K, s[0], s[1], s[2], QT.clone(), unconv, it)
 
@@ -299,7 +331,9 @@ def solve_mpc_tracking_batch(x0, x_ref, u_ref, T_pred: int = T_PRED):
 class MpcBoxResult:
     """solve_mpc_tracking_box_batch's result (device tensors): x (B,N,4), u (B,N-1,2), K0 (N-1,2,4) the
     unconstrained first gains, qp_iters (B,N-1) int32 active-set sweeps per QP, unconverged (B,) int32 QPs per lane
-    that reached max_qp_iters without settling."""
+    that reached max_qp_iters without settling.  With ``tau_max=TorqueLimit(...)``: qp_iters = active-set sweeps +
+    Newton iterations of the fallback (> max_qp_iters exactly when it ran), unconverged = the QPs that neither phase
+    finished."""
     x: torch.Tensor
     u: torch.Tensor
     K0: torch.Tensor
@@ -307,30 +341,33 @@ class MpcBoxResult:
     unconverged: torch.Tensor
 
 
-def _check_box(tau_max, T_pred, max_qp_iters):
+def _check_box(tau_max, T_pred, max_qp_iters, fallback_iters=0):
     """The torque-limited paths' arguments, refused before any device is needed (the engine's own checks)."""
-    check_box(tau_max, max_qp_iters)
+    check_box(tau_max, max_qp_iters, fallback_iters)
     check_window(T_pred, "the torque-limited QP")
 
 
 def solve_mpc_tracking_box_batch(x0, x_ref, u_ref, tau_max: float = TAU_MAX, T_pred: int = T_PRED,
                                  max_qp_iters: int = 32, Q=Q_MPC, R=R_MPC) -> MpcBoxResult:
     """Batched receding-horizon MPC with the torque limit |u_ref + u| <= tau_max on every stage of every window
-    (solve_mpc_tracking :8-69 with solver_mpc's test_constraints on): x0 (B,4) -> MpcBoxResult."""
-    _check_box(tau_max, T_pred, max_qp_iters)
+    (solve_mpc_tracking :8-69 with solver_mpc's test_constraints on): x0 (B,4) -> MpcBoxResult.  tau_max: a number,
+    or a TorqueLimit for the projected-Newton fallback (MpcBoxResult says what qp_iters and unconverged mean then)."""
+    tau_max, fb = _torque_limit(tau_max)
+    _check_box(tau_max, T_pred, max_qp_iters, fb)
     eng = _eng()
     x_ref = eng.t(x_ref).reshape(-1, 4)
     u_ref = eng.t(u_ref).reshape(-1, 2)
     x_f, u_f = _final_state(eng)
     K_all, QT, _ = eng.mpc_gains_all(x_ref, u_ref, x_f, u_f, Q, R, L=int(T_pred), nwin=x_ref.shape[0] - 1)
     x, u, it, unconv = eng.mpc_box_rollout(x0, x_ref, u_ref, x_f, u_f, Q, R, QT, K_all, float(tau_max),
-                                           int(max_qp_iters))
+                                           int(max_qp_iters), **_fb_kw(fb))
     return MpcBoxResult(x, u, K_all[:, 0].contiguous(), it, unconv)
 
 
 def solve_mpc_tracking(x0, x_ref, u_ref, T, T_pred: int = T_PRED, tau_max=None):
     """trajectory_tracking.py:8-69 -> (x_real (N,4), u_real (N-1,2)); control steps t < T-1.  tau_max: the torque
-    limit of solver_mpc's test_constraints path (None: the reference's default, no limit)."""
+    limit of solver_mpc's test_constraints path (None: the reference's default, no limit; a TorqueLimit: with the
+    projected-Newton fallback for QPs whose active set does not settle)."""
     x_ref = np.asarray(x_ref, dtype=float)
     u_ref = np.asarray(u_ref, dtype=float)
     steps = int(T) - 1
@@ -351,18 +388,20 @@ def solver_mpc(x0, A_list, B_list, Q, R, Q_T, T_pred, u_ref=None, tau_max=None):
     """trajectory_tracking.py:73-140: the window's QP solved exactly -> (U0 (2,), X_opt (T_pred,4),
     U_opt (T_pred,2)); U_opt's last row (no cost, no constraint in the reference's QP) is 0.  tau_max: the torque
     limit -tau_max <= u_t + u_ref_t <= tau_max of the test_constraints path (:87-114; needs u_ref, as the reference
-    does); None: no limit."""
+    does); None: no limit; a TorqueLimit: a QP whose active set does not settle in 32 sweeps goes on by projected
+    Newton, and the warning is printed only if that does not finish either."""
     eng = _eng()
+    tau_max, fb = _torque_limit(tau_max)
     if tau_max is not None:
         if u_ref is None:
             raise ValueError("solver_mpc needs u_ref to apply tau_max (the limit is on u_t + u_ref_t)")
-        _check_box(tau_max, T_pred, 32)
+        _check_box(tau_max, T_pred, 32, fb)
         Lw = int(T_pred)
         A = np.asarray(A_list[:Lw - 1], dtype=float).reshape(-1, 4, 4)
         B = np.asarray(B_list[:Lw - 1], dtype=float).reshape(-1, 4, 2)
         ur = np.asarray(u_ref, dtype=float).reshape(-1, 2)[:Lw - 1]
         U, X, _, conv = eng.mpc_box_qp(A, B, ur, Q, R, Q_T, np.asarray(x0, dtype=float).reshape(1, 4), Lw,
-                                       float(tau_max))
+                                       float(tau_max), **_fb_kw(fb))
         if not int(conv[0].item()):
             print("Attention! mpc solver did not settle its active set: clipped last iterate returned")
         U_opt = np.zeros((Lw, 2))

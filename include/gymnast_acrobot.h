@@ -423,6 +423,33 @@ int gym_mpc_box_rollout(const gym_model* m, const double* x0, const double* x_re
                         const double* K_all, int64_t B, int32_t N, int32_t L, double tau_max, int32_t max_qp_iters,
                         void* ws, int64_t ws_bytes, double* x_out, double* u_out, int32_t* qp_iters_out,
                         int32_t* unconverged_out, void* stream);
+/* The projected-Newton fallback of the window QP (solver_mpc with test_constraints on, trajectory_tracking.py:87-114:
+ * the reference's solver returns the minimiser of every window; the active set alone cycles on some).  A QP that has
+ * not settled after max_qp_iters active-set sweeps is not clipped and flagged but continued from that clipped
+ * (feasible) iterate by Bertsekas' projected Newton for at most fallback_iters iterations, one clamped Riccati sweep
+ * each: gradient by the costate pass, active set {u at lo, q > 0} / {u at hi, q < 0}, Newton target on that face,
+ * Armijo search (sigma 1e-4, steps 1, 1/2, ... at most 30) along the projection arc with the cost of a trial from one
+ * linear rollout.  It stops exactly: a full step that violated no bound and left the active set as it was is the
+ * minimiser.  The QP is strictly convex and its box never empty, so the minimiser exists.
+ * Same arguments, checks, workspace (gym_mpc_box_workspace) and outputs as the entry point without the suffix, plus
+ * fallback_iters >= 1 after max_qp_iters (GYM_EINVAL otherwise).  What changes in the outputs:
+ *   iterations  active-set sweeps + Newton iterations, so iterations > max_qp_iters exactly when the fallback ran;
+ *   converged / unconverged  a QP is unconverged only when neither phase finished (the fallback ran out of
+ *               iterations or its search found no step): it then returns its last feasible iterate.
+ * A QP that settles within max_qp_iters never enters the fallback and is the other entry point's QP bit for bit.
+ * Additive to ABI 18: no existing entry point or structure changed. */
+/* gym_mpc_box_qp with the fallback (trajectory_tracking.py:87-114) */
+int gym_mpc_box_qp_fallback(const double* A, const double* B_stage, const double* u_ref, int32_t S, const double Q[16],
+                            const double R[4], const double* QT, const double* x0, int64_t B, int32_t L,
+                            double tau_max, int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes,
+                            double* U, double* X, int32_t* iters_out, int32_t* converged_out, void* stream);
+/* gym_mpc_box_rollout with the fallback (trajectory_tracking.py:87-114) in every QP of the closed loop */
+int gym_mpc_box_rollout_fallback(const gym_model* m, const double* x0, const double* x_ref, const double* u_ref,
+                                 const double* x_f, const double* u_f, const double Q[16], const double R[4],
+                                 const double* QT, const double* K_all, int64_t B, int32_t N, int32_t L,
+                                 double tau_max, int32_t max_qp_iters, int32_t fallback_iters, void* ws,
+                                 int64_t ws_bytes, double* x_out, double* u_out, int32_t* qp_iters_out,
+                                 int32_t* unconverged_out, void* stream);
 
 /* ---------------- Per-lane LQR tracking: every lane tracks its own trajectory ----------------
  * (main.py task_2's result fed to task_3, per lane.)  x_opt (B,N,4) and u_opt (B,N-1,2) are the lane-major arrays a
@@ -490,6 +517,15 @@ int gym_mpc_box_lanes_rollout(const gym_model* m, const double* x_opt, const dou
                               const double* QT_dev, double tau_max, int32_t max_qp_iters, void* ws, int64_t ws_bytes,
                               double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
                               int32_t* unconverged_out, void* stream);
+/* gym_mpc_box_lanes_rollout with gym_mpc_box_qp_fallback's second phase (solver_mpc's test_constraints,
+ * trajectory_tracking.py:87-114) in every QP: fallback_iters >= 1 after max_qp_iters (GYM_EINVAL otherwise), the
+ * same workspace; qp_iters_out counts both phases, unconverged_out only the QPs that neither phase finished. */
+int gym_mpc_box_lanes_rollout_fallback(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0,
+                                       int64_t B, int32_t P, int32_t N, int32_t L, const double Q[16],
+                                       const double R[4], const double* QT_dev, double tau_max, int32_t max_qp_iters,
+                                       int32_t fallback_iters, void* ws, int64_t ws_bytes, double* x_out,
+                                       double* u_out, double* summary_out, int32_t* qp_iters_out,
+                                       int32_t* unconverged_out, void* stream);
 
 /* [host] create / destroy the events of a gym_timing; collect = add the elapsed time of every pending
  * pair (call only after the stream that recorded them has been synchronised). */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of the device code of two source trees (CPU only; needs hipcc, no GPU).
 
-    python tools/kernel_isa_diff.py OLD_TREE NEW_TREE [--source acrobot_kernels.hip] [--out DIR]
+    python tools/kernel_isa_diff.py OLD_TREE NEW_TREE [--source acrobot_kernels.hip] [--out DIR] [--allow-new]
 
 Each tree's translation unit is compiled device-only to assembly with _build.py's flags (and a fixed build id), and
 the two outputs are compared per kernel symbol rather than as whole files, because moving code between files
@@ -122,6 +122,8 @@ def main() -> int:
     ap.add_argument("new")
     ap.add_argument("--source", default="acrobot_kernels.hip", help="translation unit under csrc/")
     ap.add_argument("--out", default=None, help="directory that keeps the two assembly files")
+    ap.add_argument("--allow-new", action="store_true",
+                    help="kernels only in NEW are listed but are no difference: every kernel of OLD must be identical")
     args = ap.parse_args()
     out = args.out or tempfile.mkdtemp(prefix="isa_diff_")
     os.makedirs(out, exist_ok=True)
@@ -145,14 +147,19 @@ def main() -> int:
             print(f"differs ({', '.join(parts)}): {s}")
         else:
             same += 1
-    if old["objects"] != new["objects"]:
-        bad += 1
-        for n in sorted(set(old["objects"]) | set(new["objects"])):
-            if old["objects"].get(n) != new["objects"].get(n):
-                print(f"device object differs: {n}")
+    # an additive change (--allow-new): NEW may hold more kernels and their objects; only OLD's are compared
+    names = set(old["objects"]) if args.allow_new else set(old["objects"]) | set(new["objects"])
+    for n in sorted(names):
+        if old["objects"].get(n) != new["objects"].get(n):
+            bad += 1
+            print(f"device object differs: {n}")
     total = len(set(old["desc"]) | set(new["desc"]))
+    added = ""
+    if args.allow_new:
+        total -= len(only_new)
+        added = f", {len(only_new)} new" if only_new else ""
     ok = same == total and not bad
-    print(f"{args.source}: {same}/{total} identical" + ("" if ok else "  -- DIFFERENT"))
+    print(f"{args.source}: {same}/{total} identical{added}" + ("" if ok else "  -- DIFFERENT"))
     return 0 if ok else 1
 
 

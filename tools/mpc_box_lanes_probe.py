@@ -13,6 +13,10 @@ warm-up and 7 timed repetitions per arm unless stated; median, min, max and the 
   d  262,144 lanes x 1 start, summaries only, tau_max 18, horizon 75: time (1 warm-up, 3 repetitions) and workspace
      bytes; the ratio to the unconstrained per-lane path's 43 ms is the price of the limit.  A workspace
      above half the free device memory goes through the engine's lane chunks instead of one call.
+  f  the projected-Newton fallback (gym_mpc_box_lanes_rollout_fallback, --fallback iterations) on b's shape, 128 lanes
+     x 64 starts at tau_max 18, each against the fallback-off kernel in the same process: horizon 50 at cap 32 and
+     cap 8 (QPs reach the cap and the off arm pays for them), horizon 75 at cap 32 (none does: what the switch costs
+     a workload that never uses it).  Not in the default arms; written to profiles/mpc_box_fallback/.
 
     python tools/mpc_box_lanes_probe.py [--arms abcd] [--reps 7] [--warmup 2] [--big-lanes 262144]
                                         [--out profiles/mpc_box_lanes/probe.json]
@@ -56,9 +60,9 @@ def timed(fn, warmup, reps):
 class Call:
     """One gym_mpc_box_lanes_rollout call on preallocated buffers: x_opt (B,N,4), u_opt (B,N-1,2), x0 (B,P,4)."""
 
-    def __init__(self, eng, tt, x_opt, u_opt, x0, L, tau, cap=32, trajectories=True):
+    def __init__(self, eng, tt, x_opt, u_opt, x0, L, tau, cap=32, trajectories=True, fb=0):
         from gymnast_optimalcontrol_amd import _lib
-        self.eng, self._lib = eng, _lib
+        self.eng, self._lib, self.fb = eng, _lib, fb
         self.x_opt, self.u_opt, self.x0 = eng.t(x_opt), eng.t(u_opt), eng.t(x0)
         self.B, self.N, self.P, self.L, self.tau, self.cap = x_opt.shape[0], x_opt.shape[1], x0.shape[1], L, tau, cap
         self.Q, self.R = (np.ascontiguousarray(a, dtype=np.float64) for a in (tt.Q_MPC, tt.R_MPC))
@@ -74,11 +78,15 @@ class Call:
 
     def __call__(self):
         e, p = self.eng, self._lib.ptr
-        self._lib.check(e.lib.gym_mpc_box_lanes_rollout(
-            C.byref(e.model), self.x_opt.data_ptr(), self.u_opt.data_ptr(), self.x0.data_ptr(), self.B, self.P, self.N,
-            self.L, self.Q.ctypes.data, self.R.ctypes.data, self.QT.data_ptr(), float(self.tau), self.cap,
-            self.ws.data_ptr(), self.ws_bytes, p(self.x), p(self.u), self.sm.data_ptr(), p(self.it),
-            self.un.data_ptr(), e.stream), "gym_mpc_box_lanes_rollout")
+        head = (C.byref(e.model), self.x_opt.data_ptr(), self.u_opt.data_ptr(), self.x0.data_ptr(), self.B, self.P,
+                self.N, self.L, self.Q.ctypes.data, self.R.ctypes.data, self.QT.data_ptr(), float(self.tau), self.cap)
+        tail = (self.ws.data_ptr(), self.ws_bytes, p(self.x), p(self.u), self.sm.data_ptr(), p(self.it),
+                self.un.data_ptr(), e.stream)
+        if self.fb:
+            self._lib.check(e.lib.gym_mpc_box_lanes_rollout_fallback(*head, self.fb, *tail),
+                            "gym_mpc_box_lanes_rollout_fallback")
+        else:
+            self._lib.check(e.lib.gym_mpc_box_lanes_rollout(*head, *tail), "gym_mpc_box_lanes_rollout")
 
     def facts(self):
         out = {"workspace_MB": self.ws_bytes / 1e6, "unconverged_qps": int(self.un.sum().item()),
@@ -87,6 +95,8 @@ class Call:
             it = self.it.cpu().numpy()
             out["iteration_histogram"] = np.bincount(it.ravel(), minlength=2).tolist()
             out["qps_with_more_than_one_sweep_pct"] = float(100.0 * (it > 1).mean())
+            out["qps_past_the_cap"] = int((it > self.cap).sum())     # the fallback ran (0 without it)
+            out["max_iterations"] = int(it.max())
         return out
 
 
@@ -101,8 +111,12 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--big-lanes", type=int, default=262144)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mpc_box_lanes", "probe.json"))
+    ap.add_argument("--fallback", type=int, default=128, help="fallback_iters of arm f")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mpc_box_fallback" if args.arms == "f" else "mpc_box_lanes",
+                                "probe.json" if args.arms != "f" else "lanes_probe.json")
     from gymnast_optimalcontrol_amd import trajectory_tracking as tt
     eng = tt._eng()
     trk = np.load(os.path.join(ROOT, "tests", "golden", "tracking.npz"))
@@ -141,6 +155,31 @@ def main():
                     print(f"T_pred {T_pred} {name}: a / b = {arm['a_over_b']:.2f}", flush=True)
                 res["arms"][f"T_pred_{T_pred}_{name}"] = arm
             del ws, K_all
+        torch.cuda.empty_cache()
+
+    if "f" in args.arms:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import box_state                  # this GPU's clocks and power over arm f (sysfs, read only)
+        box = box_state.Sampler(torch.cuda.current_device(), 0.02).start()
+        box.mark()
+        x_ref, u_ref = eng.t(xr), eng.t(ur)
+        B, P = 128, 64
+        for T_pred, cap in ((50, 32), (50, 8), (75, 32)):
+            arm = {}
+            for key, fb in (("off", 0), ("fallback", args.fallback)):
+                call = Call(eng, tt, x_ref[None].expand(B, N, 4), u_ref[None].expand(B, N - 1, 2),
+                            starts.reshape(B, P, 4), T_pred, 18.0, cap=cap, fb=fb)
+                t = timed(call, args.warmup, args.reps)
+                t.update(call.facts())
+                arm[key] = t
+                line(f"f T_pred {T_pred} cap {cap} {key} (unconverged {t['unconverged_qps']}, past the cap "
+                     f"{t['qps_past_the_cap']}, iterations <= {t['max_iterations']})", t)
+                del call
+            arm["fallback_over_off"] = arm["fallback"]["median_us"] / arm["off"]["median_us"]
+            res["arms"][f"f_T_pred_{T_pred}_cap_{cap}"] = arm
+        res["box_arm_f"] = box.window() if box.available else {"unmeasured": "no sysfs channels for this device"}
+        box.stop()
+        print("box", json.dumps(res["box_arm_f"]), flush=True)
         torch.cuda.empty_cache()
 
     if "c" in args.arms:
