@@ -1,11 +1,11 @@
 // Torque-limited MPC on ONE shared reference (gym_mpc_box_qp / gym_mpc_box_rollout): the box-QP active set
 // (box_qp_lane and its three passes, which mpc_box_lanes.hpp runs per lane as well), its opt-in projected-Newton
-// fallback (box_pn_lane; the ..._fallback entry points), the stage table, the kernels (mpc_box_kernels.def.hpp) and
-// the workspace layout.  Part of the tracking_kernels.hip translation unit: included inside its anonymous
+// fallback (box_pn_lane; the ..._fallback entry points), the stage table, the kernel templates and the workspace
+// layout.  Part of the tracking_kernels.hip translation unit: included inside its anonymous
 // namespace; gym:: and Dyn come from acrobot_device.hpp, which the .hip includes ahead of the namespace.
 #pragma once
 
-#include "mpc_gains.hpp"   // M44, StageLin, disc_stage, kMpcMaxStages, wave_lds_order
+#include "mpc_gains.hpp"   // M44, chain4, StageLin, disc_stage, kMpcMaxStages, wave_lds_order
 
 // ------------------------------------------------------------------------------------------
 // Torque-limited MPC (solver_mpc with test_constraints on, :87-114): every stage of the window obeys
@@ -66,6 +66,14 @@ __device__ __forceinline__ double box_gain_dot(const double* k, double x0, doubl
     return ((k[0] * x0 + k[1] * x1) + k[2] * x2) + k[3] * x3;
 }
 
+// the state step x <- A x + b u on stage row A (A_d, then b), by value: as in/out references the passes' kernels change
+struct BoxX { double x0, x1, x2, x3; };
+__device__ __forceinline__ BoxX box_step(const double* A, double x0, double x1, double x2, double x3, double u) {
+    const double x[4] = {x0, x1, x2, x3};
+    return {chain4(A, 1, x, 1) + A[16] * u, chain4(A + 4, 1, x, 1) + A[17] * u, chain4(A + 8, 1, x, 1) + A[18] * u,
+            chain4(A + 12, 1, x, 1) + A[19] * u};
+}
+
 // clamped Riccati sweep of the lane's current stage states -> (k, d) of every stage in the workspace
 __device__ __forceinline__ void box_backward(const BoxWin& w, int Lm, const M44& Q, double r, const double* QT,
                                              double tau, const BoxWs& ws, bool all_free) {
@@ -82,15 +90,14 @@ __device__ __forceinline__ void box_backward(const BoxWin& w, int Lm, const M44&
         sn = all_free ? 0 : ws.state(t > 0 ? t - 1 : 0);
         double Pb[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) Pb[i] = ((P[4 * i] * b[0] + P[4 * i + 1] * b[1]) + P[4 * i + 2] * b[2]) + P[4 * i + 3] * b[3];
-        const double g = r + (((Pb[0] * b[0] + Pb[1] * b[1]) + Pb[2] * b[2]) + Pb[3] * b[3]);
+        for (int i = 0; i < 4; ++i) Pb[i] = chain4(P + 4 * i, 1, b, 1);
+        const double g = r + chain4(Pb, 1, b, 1);
         const double ig = 1.0 / g;
         double k[4], d;
         if (s == 0) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                k[j] = -((((Pb[0] * A[j] + Pb[1] * A[4 + j]) + Pb[2] * A[8 + j]) + Pb[3] * A[12 + j]) * ig);
-            d = -((((p[0] * b[0] + p[1] * b[1]) + p[2] * b[2]) + p[3] * b[3]) * ig);
+            for (int j = 0; j < 4; ++j) k[j] = -(chain4(Pb, 1, A + j, 4) * ig);
+            d = -(chain4(p, 1, b, 1) * ig);
         } else {
             k[0] = k[1] = k[2] = k[3] = 0.0;
             d = (s > 0 ? tau : -tau) - A[21];
@@ -104,18 +111,16 @@ __device__ __forceinline__ void box_backward(const BoxWin& w, int Lm, const M44&
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            pn[i] = (r * k[i]) * d + (((Acl[i] * v[0] + Acl[4 + i] * v[1]) + Acl[8 + i] * v[2]) + Acl[12 + i] * v[3]);
+            pn[i] = (r * k[i]) * d + chain4(Acl + i, 4, v, 1);
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                M[4 * i + j] = ((P[4 * i] * Acl[j] + P[4 * i + 1] * Acl[4 + j]) + P[4 * i + 2] * Acl[8 + j]) + P[4 * i + 3] * Acl[12 + j];
+            for (int j = 0; j < 4; ++j) M[4 * i + j] = chain4(P + 4 * i, 1, Acl + j, 4);
         }
         double Pn[16];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                Pn[4 * i + j] = (Q.v[4 * i + j] + (r * k[i]) * k[j]) +
-                                (((Acl[i] * M[j] + Acl[4 + i] * M[4 + j]) + Acl[8 + i] * M[8 + j]) + Acl[12 + i] * M[12 + j]);
+                Pn[4 * i + j] = (Q.v[4 * i + j] + (r * k[i]) * k[j]) + chain4(Acl + i, 4, M + j, 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             p[i] = pn[i];
@@ -165,25 +170,23 @@ __device__ __forceinline__ bool box_forward(const BoxWin& w, int Lm, const BoxWs
             ws.at(t, 5) = x0; ws.at(t, 6) = x1; ws.at(t, 7) = x2; ws.at(t, 8) = x3;
             ws.at(t, 9) = u;
         }
-        const double n0 = (((A[0] * x0 + A[1] * x1) + A[2] * x2) + A[3] * x3) + A[16] * u;
-        const double n1 = (((A[4] * x0 + A[5] * x1) + A[6] * x2) + A[7] * x3) + A[17] * u;
-        const double n2 = (((A[8] * x0 + A[9] * x1) + A[10] * x2) + A[11] * x3) + A[18] * u;
-        const double n3 = (((A[12] * x0 + A[13] * x1) + A[14] * x2) + A[15] * x3) + A[19] * u;
-        x0 = n0; x1 = n1; x2 = n2; x3 = n3;
+        const BoxX n = box_step(A, x0, x1, x2, x3, u);
+        x0 = n.x0; x1 = n.x1; x2 = n.x2; x3 = n.x3;
     }
     if constexpr (STORE) { ws.at(Lm, 0) = x0; ws.at(Lm, 1) = x1; ws.at(Lm, 2) = x2; ws.at(Lm, 3) = x3; }
     return viol;
 }
 
-// costate pass over the stored (x, u) and the stage-state update; returns whether any stage changed
+// costate pass over the stored (x, u) and the stage-state update; returns whether any stage changed.  PN: the
+// fallback's gradient pass (all_free = false): its state rule, the active set of (u, q), and q_t -> slot 5
+template <bool PN = false>
 __device__ __forceinline__ bool box_update(const BoxWin& w, int Lm, const M44& Q, double r, const double* QT,
                                            double tau, const BoxWs& ws, bool all_free) {
     double lam[4];
     {
         const double x[4] = {ws.at(Lm, 0), ws.at(Lm, 1), ws.at(Lm, 2), ws.at(Lm, 3)};
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            lam[i] = 2.0 * (((QT[4 * i] * x[0] + QT[4 * i + 1] * x[1]) + QT[4 * i + 2] * x[2]) + QT[4 * i + 3] * x[3]);
+        for (int i = 0; i < 4; ++i) lam[i] = 2.0 * chain4(QT + 4 * i, 1, x, 1);
     }
     bool changed = false;
     double un = ws.at(Lm - 1, 9), xn[4] = {ws.at(Lm - 1, 5), ws.at(Lm - 1, 6), ws.at(Lm - 1, 7), ws.at(Lm - 1, 8)};
@@ -200,15 +203,16 @@ __device__ __forceinline__ bool box_update(const BoxWin& w, int Lm, const M44& Q
 #pragma unroll
         for (int q = 0; q < 4; ++q) xn[q] = ws.at(tn, 5 + q);
         sn = all_free ? 0 : ws.state(tn);
-        const double q = 2.0 * r * u + (((lam[0] * A[16] + lam[1] * A[17]) + lam[2] * A[18]) + lam[3] * A[19]);
-        const int ns = s == 0 ? (u > hi ? 1 : (u < lo ? -1 : 0)) : (s > 0 ? (q < 0.0 ? 1 : 0) : (q > 0.0 ? -1 : 0));
+        const double q = 2.0 * r * u + chain4(lam, 1, A + 16, 1);
+        const int ns = PN       ? ((u <= lo && q > 0.0) ? -1 : ((u >= hi && q < 0.0) ? 1 : 0))
+                       : s == 0 ? (u > hi ? 1 : (u < lo ? -1 : 0))
+                                : (s > 0 ? (q < 0.0 ? 1 : 0) : (q > 0.0 ? -1 : 0));
         changed |= ns != s;
         ws.state(t) = ns;
+        if constexpr (PN) ws.at(t, 5) = q;                  // x_t is in registers; stage t - 1 is read already
         double nl[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            nl[i] = 2.0 * (((Q.v[4 * i] * x[0] + Q.v[4 * i + 1] * x[1]) + Q.v[4 * i + 2] * x[2]) + Q.v[4 * i + 3] * x[3]) +
-                    (((A[i] * lam[0] + A[4 + i] * lam[1]) + A[8 + i] * lam[2]) + A[12 + i] * lam[3]);
+        for (int i = 0; i < 4; ++i) nl[i] = 2.0 * chain4(Q.v + 4 * i, 1, x, 1) + chain4(A + i, 4, lam, 1);
 #pragma unroll
         for (int i = 0; i < 4; ++i) lam[i] = nl[i];
     }
@@ -218,8 +222,9 @@ __device__ __forceinline__ bool box_update(const BoxWin& w, int Lm, const M44& Q
 // ------------------------------------------------------------------------------------------
 // The fallback (FALLBACK instantiations only): a QP whose active set has not settled after max_it sweeps is continued
 // by projected Newton (Bertsekas) from its clipped iterate u, which is feasible.  One iteration:
-//   gradient   q_t by box_update's costate pass over the stored (x, u); stage t is at lo when u_t <= lo_t and q_t > 0,
-//              at hi when u_t >= hi_t and q_t < 0, free otherwise (box_pn_gradient: whether any state changed)
+//   gradient   box_update<true>: the active set's own costate pass over the stored (x, u), one loop for both, with
+//              this phase's state rule -- stage t is at lo when u_t <= lo_t and q_t > 0, at hi when u_t >= hi_t and
+//              q_t < 0, free otherwise -- and q_t kept; returns whether any state changed
 //   target     box_backward on these states, unchanged; ubar_t = k_t x_t + d_t along its own states (box_pn_target:
 //              whether a free stage of ubar lies outside its bounds)
 //   search     a = 1, 1/2, ... (kBoxPnTrials at most): u(a) = clip(u + a (ubar - u), lo, hi); the first a with
@@ -233,47 +238,6 @@ __device__ __forceinline__ bool box_update(const BoxWin& w, int Lm, const M44& Q
 // ------------------------------------------------------------------------------------------
 constexpr int kBoxPnTrials = 30;
 constexpr double kBoxPnSigma = 1e-4;
-
-// costate pass over the stored (x, u): q_t -> slot 5, the active set of (u, q) -> the stage states
-__device__ __forceinline__ bool box_pn_gradient(const BoxWin& w, int Lm, const M44& Q, double r, const double* QT,
-                                                double tau, const BoxWs& ws) {
-    double lam[4];
-    {
-        const double x[4] = {ws.at(Lm, 0), ws.at(Lm, 1), ws.at(Lm, 2), ws.at(Lm, 3)};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            lam[i] = 2.0 * (((QT[4 * i] * x[0] + QT[4 * i + 1] * x[1]) + QT[4 * i + 2] * x[2]) + QT[4 * i + 3] * x[3]);
-    }
-    bool changed = false;
-    double un = ws.at(Lm - 1, 9), xn[4] = {ws.at(Lm - 1, 5), ws.at(Lm - 1, 6), ws.at(Lm - 1, 7), ws.at(Lm - 1, 8)};
-    int sn = ws.state(Lm - 1);                              // (x, u, state) one stage ahead, as in box_backward
-    for (int t = Lm - 1; t >= 0; --t) {
-        const double* A = w.row(t);
-        const double f = A[21];
-        const double hi = tau - f, lo = -tau - f;
-        const double u = un;
-        const double x[4] = {xn[0], xn[1], xn[2], xn[3]};
-        const int s = sn;
-        const int tn = t > 0 ? t - 1 : 0;
-        un = ws.at(tn, 9);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) xn[q] = ws.at(tn, 5 + q);
-        sn = ws.state(tn);
-        const double q = 2.0 * r * u + (((lam[0] * A[16] + lam[1] * A[17]) + lam[2] * A[18]) + lam[3] * A[19]);
-        const int ns = (u <= lo && q > 0.0) ? -1 : ((u >= hi && q < 0.0) ? 1 : 0);
-        changed |= ns != s;
-        ws.state(t) = ns;
-        ws.at(t, 5) = q;                                    // x_t is in registers; stage t - 1 is read already
-        double nl[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            nl[i] = 2.0 * (((Q.v[4 * i] * x[0] + Q.v[4 * i + 1] * x[1]) + Q.v[4 * i + 2] * x[2]) + Q.v[4 * i + 3] * x[3]) +
-                    (((A[i] * lam[0] + A[4 + i] * lam[1]) + A[8 + i] * lam[2]) + A[12 + i] * lam[3]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lam[i] = nl[i];
-    }
-    return changed;
-}
 
 // forward pass of box_backward's (k, d) along its own states: ubar_t -> slot 6; whether a free ubar_t is out of bounds
 __device__ __forceinline__ bool box_pn_target(const BoxWin& w, int Lm, const BoxWs& ws, double tau, double x0,
@@ -296,11 +260,8 @@ __device__ __forceinline__ bool box_pn_target(const BoxWin& w, int Lm, const Box
         const double u = s == 0 ? box_gain_dot(k, x0, x1, x2, x3) + d : d;
         viol |= (s == 0) & ((u > tau - A[21]) | (u < -tau - A[21]));
         ws.at(t, 6) = u;
-        const double n0 = (((A[0] * x0 + A[1] * x1) + A[2] * x2) + A[3] * x3) + A[16] * u;
-        const double n1 = (((A[4] * x0 + A[5] * x1) + A[6] * x2) + A[7] * x3) + A[17] * u;
-        const double n2 = (((A[8] * x0 + A[9] * x1) + A[10] * x2) + A[11] * x3) + A[18] * u;
-        const double n3 = (((A[12] * x0 + A[13] * x1) + A[14] * x2) + A[15] * x3) + A[19] * u;
-        x0 = n0; x1 = n1; x2 = n2; x3 = n3;
+        const BoxX n = box_step(A, x0, x1, x2, x3, u);
+        x0 = n.x0; x1 = n.x1; x2 = n.x2; x3 = n.x3;
     }
     return viol;
 }
@@ -333,20 +294,15 @@ __device__ __forceinline__ void box_pn_trial(const BoxWin& w, int Lm, const M44&
         const double x[4] = {x0, x1, x2, x3};
         double xq = 0.0;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            xq += x[i] * (((Q.v[4 * i] * x0 + Q.v[4 * i + 1] * x1) + Q.v[4 * i + 2] * x2) + Q.v[4 * i + 3] * x3);
+        for (int i = 0; i < 4; ++i) xq += x[i] * chain4(Q.v + 4 * i, 1, x, 1);
         cost += xq + (r * dl) * dl;
-        const double n0 = (((A[0] * x0 + A[1] * x1) + A[2] * x2) + A[3] * x3) + A[16] * dl;
-        const double n1 = (((A[4] * x0 + A[5] * x1) + A[6] * x2) + A[7] * x3) + A[17] * dl;
-        const double n2 = (((A[8] * x0 + A[9] * x1) + A[10] * x2) + A[11] * x3) + A[18] * dl;
-        const double n3 = (((A[12] * x0 + A[13] * x1) + A[14] * x2) + A[15] * x3) + A[19] * dl;
-        x0 = n0; x1 = n1; x2 = n2; x3 = n3;
+        const BoxX n = box_step(A, x0, x1, x2, x3, dl);
+        x0 = n.x0; x1 = n.x1; x2 = n.x2; x3 = n.x3;
     }
     const double x[4] = {x0, x1, x2, x3};
     double xq = 0.0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-        xq += x[i] * (((QT[4 * i] * x0 + QT[4 * i + 1] * x1) + QT[4 * i + 2] * x2) + QT[4 * i + 3] * x3);
+    for (int i = 0; i < 4; ++i) xq += x[i] * chain4(QT + 4 * i, 1, x, 1);
     slope = sl;
     quad = cost + xq;
 }
@@ -366,11 +322,8 @@ __device__ __forceinline__ void box_pn_store(const BoxWin& w, int Lm, double tau
         if (t == 0) u_first = v;
         ws.at(t, 5) = x0; ws.at(t, 6) = x1; ws.at(t, 7) = x2; ws.at(t, 8) = x3;
         ws.at(t, 9) = v;
-        const double n0 = (((A[0] * x0 + A[1] * x1) + A[2] * x2) + A[3] * x3) + A[16] * v;
-        const double n1 = (((A[4] * x0 + A[5] * x1) + A[6] * x2) + A[7] * x3) + A[17] * v;
-        const double n2 = (((A[8] * x0 + A[9] * x1) + A[10] * x2) + A[11] * x3) + A[18] * v;
-        const double n3 = (((A[12] * x0 + A[13] * x1) + A[14] * x2) + A[15] * x3) + A[19] * v;
-        x0 = n0; x1 = n1; x2 = n2; x3 = n3;
+        const BoxX n = box_step(A, x0, x1, x2, x3, v);
+        x0 = n.x0; x1 = n.x1; x2 = n.x2; x3 = n.x3;
     }
     ws.at(Lm, 0) = x0; ws.at(Lm, 1) = x1; ws.at(Lm, 2) = x2; ws.at(Lm, 3) = x3;
 }
@@ -388,7 +341,7 @@ __device__ __forceinline__ void box_pn_lane(const BoxWin& w, int Lm, const M44& 
     for (int n = 0; n <= fb_it; ++n) {
         if (!__any(active)) break;
         if (active) {
-            const bool changed = box_pn_gradient(w, Lm, Q, r, QT, tau, ws);
+            const bool changed = box_update<true>(w, Lm, Q, r, QT, tau, ws, false);
             if (n > 0 && full && !changed) {
                 conv = true;
                 active = false;
@@ -503,25 +456,113 @@ __global__ __launch_bounds__(64) void k_mpc_box_stages(Dyn m, const double* __re
 
 constexpr int kBoxMaxLm = kMpcMaxStages - 3;   // L - 1 <= 253 stages per window (L + 2 <= 256)
 
-// k_mpc_box_qp, k_mpc_box_rollout and their fallback twins k_mpc_box_qp_fb, k_mpc_box_rollout_fb: one text, two passes
-#define GYM_BOX_K(name) name
-#define GYM_BOX_FB false
-#define GYM_BOX_FB_PARAM
-#define GYM_BOX_FB_ARG
-#include "mpc_box_kernels.def.hpp"
-#undef GYM_BOX_K
-#undef GYM_BOX_FB
-#undef GYM_BOX_FB_PARAM
-#undef GYM_BOX_FB_ARG
-#define GYM_BOX_K(name) name##_fb
-#define GYM_BOX_FB true
-#define GYM_BOX_FB_PARAM int fb_it,
-#define GYM_BOX_FB_ARG , fb_it
-#include "mpc_box_kernels.def.hpp"
-#undef GYM_BOX_K
-#undef GYM_BOX_FB
-#undef GYM_BOX_FB_PARAM
-#undef GYM_BOX_FB_ARG
+// The kernels below and k_mpc_box_lane_rollout (mpc_box_lanes.hpp) are kernel templates with two instantiations:
+// k<false>, the active set alone, and k<true, int>, whose pack Fb is the one parameter fb_it after max_it, handed to
+// box_qp_lane's fallback.  The kernel itself is the template: thin __global__ wrappers around a shared body gave the
+// fallback-off kernels other register allocation; instantiations do not (tools/kernel_isa_diff.py).
+
+// A batch of QPs on one window: x0 (B,4) -> U (B,L-1,2), X (B,L,4), iterations and converged flag per QP
+template <bool FB, class... Fb>
+__global__ __launch_bounds__(64) void k_mpc_box_qp(BoxTable tb, int L, M44 Q, double r,
+                                                   const double* __restrict__ QT, double tau, int max_it,
+                                                   Fb... fb_it, const double* __restrict__ x0, int64_t B,
+                                                   double* wsd, int32_t* wst, int64_t Bp, double* __restrict__ U,
+                                                   double* __restrict__ X, int32_t* __restrict__ iters_out,
+                                                   int32_t* __restrict__ conv_out) {
+    __shared__ double rows[kBoxMaxLm * kBoxRow];
+    const int ln = threadIdx.x;
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + ln;
+    const bool valid = l < B;
+    const int Lm = L - 1;
+    for (int idx = ln; idx < Lm * kBoxRow; idx += 64) rows[idx] = box_row_elem(tb, idx / kBoxRow, idx % kBoxRow);
+    wave_lds_order();
+    const BoxWin w{rows, nullptr, 0, Lm};
+    const BoxWs ws{wsd, wst, Bp, l};
+    const int64_t lr = valid ? l : 0;
+    double u_first;
+    int iters;
+    bool conv;
+    box_qp_lane<true, FB>(w, Lm, Q, r, QT, tau, max_it, ws, valid, x0[4 * lr], x0[4 * lr + 1], x0[4 * lr + 2],
+                          x0[4 * lr + 3], u_first, iters, conv, fb_it...);
+    if (!valid) return;
+    double* Ul = U + 2 * (int64_t)Lm * l;
+    double* Xl = X + 4 * (int64_t)L * l;
+    for (int t = 0; t < Lm; ++t) {
+        Ul[2 * t] = box_clip0(w.row(t)[20], tau);
+        Ul[2 * t + 1] = ws.at(t, 9);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) Xl[4 * t + q] = ws.at(t, 5 + q);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) Xl[4 * Lm + q] = ws.at(Lm, q);
+    iters_out[l] = iters;
+    conv_out[l] = conv ? 1 : 0;
+}
+
+// The torque-limited closed loop (solve_mpc_tracking :43-67), one trajectory per lane.  Per control step s: e = x -
+// x_ref[s], the window's QP (rows s .. s+L-2 of the stage table, the pad past its end; first iterate from K_all's
+// window s), u_real[s] = u_ref[s] + u_0, one RK4 step.  Lane-major x (B,N,4), u (B,N-1,2), qp_iters (B,N-1) and the
+// lane's count of unconverged QPs.  The wavefront keeps the window's rows in an LDS ring (one new row per step) and
+// loads the window's Kw (row 1 of each gain) at the top of the step.  With the fallback qp_iters counts both phases
+// and unconverged only the QPs that neither phase finished.
+template <bool FB, class... Fb>
+__global__ __launch_bounds__(64) void k_mpc_box_rollout(Dyn m, BoxTable tb, int L, M44 Q, double r,
+                                                        const double* __restrict__ QT, double tau, int max_it,
+                                                        Fb... fb_it, const double* __restrict__ x0,
+                                                        const double* __restrict__ x_ref,
+                                                        const double* __restrict__ K_all, int64_t B, int N,
+                                                        double* wsd, int32_t* wst, int64_t Bp,
+                                                        double* __restrict__ xo, double* __restrict__ uo,
+                                                        int32_t* __restrict__ it_out, int32_t* __restrict__ unconv_out) {
+    __shared__ double rows[kBoxMaxLm * kBoxRow];
+    __shared__ double kw[kBoxMaxLm * 4];
+    const int ln = threadIdx.x;
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + ln;
+    const bool valid = l < B;
+    const int64_t lr = valid ? l : 0;
+    const int T = N - 1, Lm = L - 1;
+    const BoxWs ws{wsd, wst, Bp, l};
+    double2* xl = reinterpret_cast<double2*>(xo + 4 * (int64_t)N * lr);
+    double2* ul = reinterpret_cast<double2*>(uo + 2 * (int64_t)T * lr);
+    int32_t* il = it_out + (int64_t)T * lr;
+    double n0 = x0[4 * lr], n1 = x0[4 * lr + 1], n2 = x0[4 * lr + 2], n3 = x0[4 * lr + 3];
+    if (valid) {
+        xl[0] = make_double2(n0, n1);
+        xl[1] = make_double2(n2, n3);
+    }
+    const gym::PolyRegs pk = gym::poly_vgprs();
+    int unconv = 0;
+    BoxWin w{rows, kw, 0, Lm};
+    for (int s = 0; s < T; ++s) {
+        wave_lds_order();                               // the previous step's LDS reads are done
+        if (s == 0) {
+            for (int idx = ln; idx < Lm * kBoxRow; idx += 64) rows[idx] = box_row_elem(tb, idx / kBoxRow, idx % kBoxRow);
+        } else {                                        // stage s + Lm - 1 replaces stage s - 1 in the ring
+            if (ln < kBoxRow) rows[kBoxRow * w.base + ln] = box_row_elem(tb, s + Lm - 1, ln);
+            w.base = w.base + 1 == Lm ? 0 : w.base + 1;
+        }
+        const double* Ks = K_all + 8 * (int64_t)s * Lm;
+        for (int idx = ln; idx < 4 * Lm; idx += 64) kw[idx] = Ks[8 * (idx >> 2) + 4 + (idx & 3)];
+        wave_lds_order();
+        const double* r4 = x_ref + 4 * (int64_t)s;
+        const double* f = w.row(0) + 20;                // u_ref[s]
+        double u1;
+        int iters;
+        bool conv;
+        box_qp_lane<false, FB>(w, Lm, Q, r, QT, tau, max_it, ws, valid, n0 - r4[0], n1 - r4[1], n2 - r4[2],
+                               n3 - r4[3], u1, iters, conv, fb_it...);
+        if (valid) {
+            const double v0 = box_apply(f[0], box_clip0(f[0], tau), tau), v1 = box_apply(f[1], u1, tau);
+            ul[s] = make_double2(v0, v1);
+            il[s] = iters;
+            unconv += conv ? 0 : 1;
+            gym::rk4(m, n0, n1, n2, n3, v1, pk);
+            xl[2 * (s + 1)] = make_double2(n0, n1);
+            xl[2 * (s + 1) + 1] = make_double2(n2, n3);
+        }
+    }
+    if (valid) unconv_out[l] = unconv;
+}
 
 // workspace of B lanes, windows of L stages, a stage table of `rows` rows: table, then per-lane doubles, then states
 struct BoxLayout {

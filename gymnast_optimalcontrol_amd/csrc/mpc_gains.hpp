@@ -5,7 +5,7 @@
 // acrobot_device.hpp, which the .hip includes ahead of the namespace (under its GYM_HORNER_VOP3 policy).
 #pragma once
 
-#include "tracking_dense.hpp"   // M44, M22
+#include "tracking_dense.hpp"   // M44, M22, chain4
 
 // ------------------------------------------------------------------------------------------
 // Fused MPC gains (solve_mpc_tracking :14-38 + the exact solution of every control step's QP): one launch.
@@ -126,13 +126,13 @@ __device__ __forceinline__ void wave_lds_order() {   // LDS writes of this wavef
 }
 // (X Y)[i][j], (X Y')[i][j], (X' Y)[i][j] from 16-double LDS matrices (row-major)
 __device__ __forceinline__ double dot_xy(const double* X, const double* Y, int i, int j) {
-    return ((X[4 * i] * Y[j] + X[4 * i + 1] * Y[4 + j]) + X[4 * i + 2] * Y[8 + j]) + X[4 * i + 3] * Y[12 + j];
+    return chain4(X + 4 * i, 1, Y + j, 4);
 }
 __device__ __forceinline__ double dot_xyt(const double* X, const double* Y, int i, int j) {
-    return ((X[4 * i] * Y[4 * j] + X[4 * i + 1] * Y[4 * j + 1]) + X[4 * i + 2] * Y[4 * j + 2]) + X[4 * i + 3] * Y[4 * j + 3];
+    return chain4(X + 4 * i, 1, Y + 4 * j, 1);
 }
 __device__ __forceinline__ double dot_xty(const double* X, const double* Y, int i, int j) {
-    return ((X[i] * Y[j] + X[4 + i] * Y[4 + j]) + X[8 + i] * Y[8 + j]) + X[12 + i] * Y[12 + j];
+    return chain4(X + i, 4, Y + j, 4);
 }
 
 // The doubling's initial triple on the pad (lane 4i+j: entry (i, j) of A_0, G_0, H_0)

@@ -7,6 +7,13 @@
 struct M44 { double v[16]; };
 struct M22 { double v[4]; };
 
+// The 4-term sum of every dense product in this translation unit, a and b read at strides sa and sb (1 along a row,
+// 4 or 2 down a column): ((a0 b0 + a1 b1) + a2 b2) + a3 b3, left to right.  The bit-for-bit contracts between the
+// kernels rest on this order, so it is written here and nowhere else.
+__device__ __forceinline__ double chain4(const double* a, int sa, const double* b, int sb) {
+    return ((a[0] * b[0] + a[sa] * b[sb]) + a[2 * sa] * b[2 * sb]) + a[3 * sa] * b[3 * sb];
+}
+
 // one step of the reference's recursion (trajectory_tracking.py:158-160 / :195-200):
 //   aux1 = R + B'PB, aux2 = B'PA, K = -inv(aux1) aux2, P <- Q + A'PA + (A'PB) K
 __device__ __forceinline__ void lqr_step(const double* A, const double* Bm, double* P, const M44& Q, const M22& R,
@@ -15,21 +22,17 @@ __device__ __forceinline__ void lqr_step(const double* A, const double* Bm, doub
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            PA[4 * i + j] = ((P[4 * i] * A[j] + P[4 * i + 1] * A[4 + j]) + P[4 * i + 2] * A[8 + j]) + P[4 * i + 3] * A[12 + j];
+        for (int j = 0; j < 4; ++j) PA[4 * i + j] = chain4(P + 4 * i, 1, A + j, 4);
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-            PB[2 * i + j] = ((P[4 * i] * Bm[j] + P[4 * i + 1] * Bm[2 + j]) + P[4 * i + 2] * Bm[4 + j]) + P[4 * i + 3] * Bm[6 + j];
+        for (int j = 0; j < 2; ++j) PB[2 * i + j] = chain4(P + 4 * i, 1, Bm + j, 2);
     }
     double a1[4], a2[8];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-            a1[2 * i + j] = R.v[2 * i + j] + (((Bm[i] * PB[j] + Bm[2 + i] * PB[2 + j]) + Bm[4 + i] * PB[4 + j]) + Bm[6 + i] * PB[6 + j]);
+        for (int j = 0; j < 2; ++j) a1[2 * i + j] = R.v[2 * i + j] + chain4(Bm + i, 2, PB + j, 2);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            a2[4 * i + j] = ((Bm[i] * PA[j] + Bm[2 + i] * PA[4 + j]) + Bm[4 + i] * PA[8 + j]) + Bm[6 + i] * PA[12 + j];
+        for (int j = 0; j < 4; ++j) a2[4 * i + j] = chain4(Bm + i, 2, PA + j, 4);
     }
     const double idet = 1.0 / (a1[0] * a1[3] - a1[1] * a1[2]);
     const double i00 = a1[3] * idet, i01 = -a1[1] * idet, i10 = -a1[2] * idet, i11 = a1[0] * idet;
@@ -43,9 +46,8 @@ __device__ __forceinline__ void lqr_step(const double* A, const double* Bm, doub
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const double apa = ((A[i] * PA[j] + A[4 + i] * PA[4 + j]) + A[8 + i] * PA[8 + j]) + A[12 + i] * PA[12 + j];
-            const double apb0 = ((A[i] * PB[0] + A[4 + i] * PB[2]) + A[8 + i] * PB[4]) + A[12 + i] * PB[6];
-            const double apb1 = ((A[i] * PB[1] + A[4 + i] * PB[3]) + A[8 + i] * PB[5]) + A[12 + i] * PB[7];
+            const double apa = chain4(A + i, 4, PA + j, 4);
+            const double apb0 = chain4(A + i, 4, PB, 2), apb1 = chain4(A + i, 4, PB + 1, 2);
             nP[4 * i + j] = (Q.v[4 * i + j] + apa) + (apb0 * K[j] + apb1 * K[4 + j]);
         }
 #pragma unroll
@@ -110,6 +112,8 @@ __global__ __launch_bounds__(64) void k_dare_fixed_point(const double* __restric
     for (int n = 0; n < max_iter; ++n) {
         if (own) sP[ln] = P;
         __syncthreads();
+        // chain4's sum, written out where a lane-dependent i or j picks the operands (and for PB beside PA): through
+        // the helper this kernel gets other register allocation (tools/kernel_isa_diff.py), so these six stay
         const double* Pi = sP + 4 * i;   // row i of P
         const double PA = ((Pi[0] * a[j] + Pi[1] * a[4 + j]) + Pi[2] * a[8 + j]) + Pi[3] * a[12 + j];
         const double PB0 = ((Pi[0] * b[0] + Pi[1] * b[2]) + Pi[2] * b[4]) + Pi[3] * b[6];
@@ -123,11 +127,8 @@ __global__ __launch_bounds__(64) void k_dare_fixed_point(const double* __restric
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
-            for (int c = 0; c < 2; ++c)
-                a1[2 * r + c] = R.v[2 * r + c] + (((b[r] * sPB[c] + b[2 + r] * sPB[2 + c]) + b[4 + r] * sPB[4 + c]) +
-                                                  b[6 + r] * sPB[6 + c]);
-        const double a20 = ((b[0] * sPA[j] + b[2] * sPA[4 + j]) + b[4] * sPA[8 + j]) + b[6] * sPA[12 + j];
-        const double a21 = ((b[1] * sPA[j] + b[3] * sPA[4 + j]) + b[5] * sPA[8 + j]) + b[7] * sPA[12 + j];
+            for (int c = 0; c < 2; ++c) a1[2 * r + c] = R.v[2 * r + c] + chain4(b + r, 2, sPB + c, 2);
+        const double a20 = chain4(b, 2, sPA + j, 4), a21 = chain4(b + 1, 2, sPA + j, 4);
         const double idet = 1.0 / (a1[0] * a1[3] - a1[1] * a1[2]);
         const double i00 = a1[3] * idet, i01 = -a1[1] * idet, i10 = -a1[2] * idet, i11 = a1[0] * idet;
         const double K0 = -(i00 * a20 + i01 * a21), K1 = -(i10 * a20 + i11 * a21);
@@ -155,16 +156,14 @@ __global__ void k_lq_forward(const double* __restrict__ A, const double* __restr
     double x[4] = {x0[0], x0[1], x0[2], x0[3]}, Ad[16], Bd[8];
     for (int s = 0; s < L - 1; ++s) {
         const double* k = K + 8 * s;
-        const double u0 = ((k[0] * x[0] + k[1] * x[1]) + k[2] * x[2]) + k[3] * x[3];
-        const double u1 = ((k[4] * x[0] + k[5] * x[1]) + k[6] * x[2]) + k[7] * x[3];
+        const double u0 = chain4(k, 1, x, 1), u1 = chain4(k + 4, 1, x, 1);
         X[4 * s] = x[0]; X[4 * s + 1] = x[1]; X[4 * s + 2] = x[2]; X[4 * s + 3] = x[3];
         U[2 * s] = u0; U[2 * s + 1] = u1;
         load_stage(A, Bm, s, S, Ap, Bp, disc, dt, Ad, Bd);
         double n[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            n[i] = (((Ad[4 * i] * x[0] + Ad[4 * i + 1] * x[1]) + Ad[4 * i + 2] * x[2]) + Ad[4 * i + 3] * x[3]) +
-                   (Bd[2 * i] * u0 + Bd[2 * i + 1] * u1);
+            n[i] = chain4(Ad + 4 * i, 1, x, 1) + (Bd[2 * i] * u0 + Bd[2 * i + 1] * u1);
         x[0] = n[0]; x[1] = n[1]; x[2] = n[2]; x[3] = n[3];
     }
     X[4 * (L - 1)] = x[0]; X[4 * (L - 1) + 1] = x[1]; X[4 * (L - 1) + 2] = x[2]; X[4 * (L - 1) + 3] = x[3];

@@ -151,7 +151,7 @@ int gym_mpc_box_workspace(int64_t B, int32_t L, int32_t rows, int64_t* bytes_out
     return 0;
 }
 
-// fallback_iters = 0: the active set alone (k_mpc_box_qp); >= 1: with the projected-Newton fallback (k_mpc_box_qp_fb)
+// fallback_iters = 0: the active set alone, k_mpc_box_qp<false>; >= 1: with the projected-Newton fallback, <true, int>
 static int box_qp_launch(const double* A, const double* Bm, const double* u_ref, int32_t S, const double Q[16],
                          const double R[4], const double* QT, const double* x0, int64_t B, int32_t L, double tau_max,
                          int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes, double* U, double* X,
@@ -171,11 +171,12 @@ static int box_qp_launch(const double* A, const double* Bm, const double* u_ref,
     const dim3 grid((unsigned)(w.lo.Bp / 64));
     const BoxTable tb{w.A, w.Bm, w.ur, S - 1};
     if (fallback_iters)
-        hipLaunchKernelGGL(k_mpc_box_qp_fb, grid, dim3(64), 0, st, tb, L, m44(Q), R[3], QT, tau_max, max_qp_iters,
-                           fallback_iters, x0, B, w.d, w.st, w.lo.Bp, U, X, iters_out, converged_out);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mpc_box_qp<true, int>), grid, dim3(64), 0, st, tb, L, m44(Q), R[3], QT,
+                           tau_max, max_qp_iters, fallback_iters, x0, B, w.d, w.st, w.lo.Bp, U, X, iters_out,
+                           converged_out);
     else
-        hipLaunchKernelGGL(k_mpc_box_qp, grid, dim3(64), 0, st, tb, L, m44(Q), R[3], QT, tau_max, max_qp_iters, x0, B,
-                           w.d, w.st, w.lo.Bp, U, X, iters_out, converged_out);
+        hipLaunchKernelGGL(k_mpc_box_qp<false>, grid, dim3(64), 0, st, tb, L, m44(Q), R[3], QT, tau_max, max_qp_iters,
+                           x0, B, w.d, w.st, w.lo.Bp, U, X, iters_out, converged_out);
     return launch_status();
 }
 
@@ -214,11 +215,11 @@ static int box_rollout_launch(const gym_model* m, const double* x0, const double
     const dim3 grid((unsigned)(w.lo.Bp / 64));
     const BoxTable tb{w.A, w.Bm, w.ur, S};
     if (fallback_iters)
-        hipLaunchKernelGGL(k_mpc_box_rollout_fb, grid, dim3(64), 0, st, Dyn(*m), tb, L, m44(Q), R[3], QT, tau_max,
-                           max_qp_iters, fallback_iters, x0, x_ref, K_all, B, N, w.d, w.st, w.lo.Bp, x_out, u_out,
-                           qp_iters_out, unconverged_out);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mpc_box_rollout<true, int>), grid, dim3(64), 0, st, Dyn(*m), tb, L,
+                           m44(Q), R[3], QT, tau_max, max_qp_iters, fallback_iters, x0, x_ref, K_all, B, N, w.d, w.st,
+                           w.lo.Bp, x_out, u_out, qp_iters_out, unconverged_out);
     else
-        hipLaunchKernelGGL(k_mpc_box_rollout, grid, dim3(64), 0, st, Dyn(*m), tb, L, m44(Q), R[3], QT, tau_max,
+        hipLaunchKernelGGL(k_mpc_box_rollout<false>, grid, dim3(64), 0, st, Dyn(*m), tb, L, m44(Q), R[3], QT, tau_max,
                            max_qp_iters, x0, x_ref, K_all, B, N, w.d, w.st, w.lo.Bp, x_out, u_out, qp_iters_out,
                            unconverged_out);
     return launch_status();
@@ -352,17 +353,17 @@ static int box_lanes_launch(const gym_model* m, const double* x_opt, const doubl
     const int nblk = (P + 63) / 64;                        // B nblk <= B P <= GYM_MAX_BP: far below the grid limit
     const size_t lds = sizeof(double) * (kBoxRow + 4) * (L - 1);
     const dim3 grid((unsigned)(B * nblk));
-    const double2* xo2 = reinterpret_cast<const double2*>(x_opt);
-    const double2* uo2 = reinterpret_cast<const double2*>(u_opt);
+    const double2 *xo2 = reinterpret_cast<const double2*>(x_opt), *uo2 = reinterpret_cast<const double2*>(u_opt);
     if (fallback_iters)
-        hipLaunchKernelGGL(k_mpc_box_lane_rollout_fb, grid, dim3(64), lds, (hipStream_t)s, Dyn(*m), m44(Q), R[3],
-                           QT_dev, tau_max, max_qp_iters, fallback_iters, xo2, uo2, x0, (int)P, (int)N, (int)L, nblk,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mpc_box_lane_rollout<true, int>), grid, dim3(64), lds, (hipStream_t)s,
+                           Dyn(*m), m44(Q), R[3], QT_dev, tau_max, max_qp_iters, fallback_iters, xo2, uo2, x0, (int)P,
+                           (int)N, (int)L, nblk, ws_at<double>(ws, 0), ws_at<int32_t>(ws, lo.off_st), x_out, u_out,
+                           summary_out, qp_iters_out, unconverged_out);
+    else
+        hipLaunchKernelGGL(k_mpc_box_lane_rollout<false>, grid, dim3(64), lds, (hipStream_t)s, Dyn(*m), m44(Q), R[3],
+                           QT_dev, tau_max, max_qp_iters, xo2, uo2, x0, (int)P, (int)N, (int)L, nblk,
                            ws_at<double>(ws, 0), ws_at<int32_t>(ws, lo.off_st), x_out, u_out, summary_out,
                            qp_iters_out, unconverged_out);
-    else
-        hipLaunchKernelGGL(k_mpc_box_lane_rollout, grid, dim3(64), lds, (hipStream_t)s, Dyn(*m), m44(Q), R[3], QT_dev,
-                           tau_max, max_qp_iters, xo2, uo2, x0, (int)P, (int)N, (int)L, nblk, ws_at<double>(ws, 0),
-                           ws_at<int32_t>(ws, lo.off_st), x_out, u_out, summary_out, qp_iters_out, unconverged_out);
     return launch_status();
 }
 

@@ -2,6 +2,7 @@
 """Per-kernel comparison of the device code of two source trees (CPU only; needs hipcc, no GPU).
 
     python tools/kernel_isa_diff.py OLD_TREE NEW_TREE [--source acrobot_kernels.hip] [--out DIR] [--allow-new]
+                                    [--rename OLD=NEW ...]
 
 Each tree's translation unit is compiled device-only to assembly with _build.py's flags (and a fixed build id), and
 the two outputs are compared per kernel symbol rather than as whole files, because moving code between files
@@ -15,6 +16,12 @@ Local labels are renumbered first (.LBB<f>_<n> carries the function's ordinal <f
 is ignored, the kernel symbol sets must be equal, and so must the device-side objects (globals, read-only data)
 as a set.  Every device function of these translation units is inlined into its kernels, so "identical" here means
 that only host code differs between the trees.  OLD_TREE / NEW_TREE may also be an assembly file (*.s) already made.
+
+A kernel whose name changed is paired by --rename OLD=NEW (repeatable).  Each side is the kernel's mangled symbol or
+any part of it that no other kernel's symbol contains, e.g. --rename k_mpc_box_qp_fb=k_mpc_box_qpILb1E for a twin
+kernel that became the template instantiation k_mpc_box_qp<true, ...>.  The pair is compared like any other kernel,
+with the symbol's own name masked in body, descriptor and metadata; a side that selects no kernel, or more than one,
+is an error (exit 2).
 
 Prints one result line, e.g. "acrobot_kernels.hip: 106/106 identical", and exits 1 on any difference.
 """
@@ -116,7 +123,12 @@ def parse(path: str) -> dict:
     return {"body": body, "desc": desc, "meta": meta, "objects": objects}
 
 
-def main() -> int:
+def pick(symbols, part: str) -> list:
+    """The kernel symbols that are, or contain, `part`: a rename needs exactly one."""
+    return [part] if part in symbols else sorted(s for s in symbols if part in s)
+
+
+def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old")
     ap.add_argument("new")
@@ -124,7 +136,9 @@ def main() -> int:
     ap.add_argument("--out", default=None, help="directory that keeps the two assembly files")
     ap.add_argument("--allow-new", action="store_true",
                     help="kernels only in NEW are listed but are no difference: every kernel of OLD must be identical")
-    args = ap.parse_args()
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="kernel OLD of the old side is kernel NEW of the new side (symbols, or unique parts of them)")
+    args = ap.parse_args(argv)
     out = args.out or tempfile.mkdtemp(prefix="isa_diff_")
     os.makedirs(out, exist_ok=True)
     stem = os.path.splitext(args.source)[0]
@@ -133,6 +147,22 @@ def main() -> int:
         asm = tree if tree.endswith(".s") else compile_asm(tree, args.source, os.path.join(out, f"{stem}.{tag}.s"))
         sides.append(parse(asm))
     old, new = sides
+    pairs = []
+    for pair in args.rename:
+        o, sep, n = pair.partition("=")
+        if not (o and sep and n):
+            ap.error(f"--rename: {pair!r} is not OLD=NEW")
+        for part, side, tag in ((o, old, "OLD"), (n, new, "NEW")):
+            hits = pick(side["desc"], part)
+            if len(hits) != 1:
+                ap.error(f"--rename: {part!r} selects {len(hits)} kernels of {tag}" + "".join(f"\n  {h}" for h in hits))
+            pairs.append(hits[0])
+    for o, n in zip(pairs[::2], pairs[1::2]):    # NEW's kernel takes OLD's symbol, both with their own name masked
+        if o != n and o in new["desc"]:
+            ap.error(f"--rename: NEW has a kernel {o} of its own")
+        for p in ("body", "desc", "meta"):
+            old[p][o] = old[p][o].replace(o, "<kernel>")
+            new[p][o] = new[p].pop(n).replace(n, "<kernel>")
     bad = 0
     only_old, only_new = sorted(set(old["desc"]) - set(new["desc"])), sorted(set(new["desc"]) - set(old["desc"]))
     for s in only_old:
