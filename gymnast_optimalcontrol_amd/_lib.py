@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("GYM_LIB_PATH") or _build.LIB_PATH
 
 # exported symbols, in include/gymnast_acrobot.h order (tests check every one is present)
 EXPORTS = (
-    "gym_abi_version", "gym_build_id", "gym_model_from_params",
+    "gym_abi_version", "gym_build_id", "gym_model_from_params", "gym_models_from_params",
     "gym_continuous_dynamics", "gym_rk4_step", "gym_jacobians", "gym_stage_cost_derivs",
     "gym_pack_lanes", "gym_unpack_lanes", "gym_unpack_gains",
     "gym_rollout_open_loop", "gym_closed_loop", "gym_total_cost", "gym_backward_sweep", "gym_linearize",
@@ -34,6 +34,7 @@ EXPORTS = (
     "gym_mpc_lanes_gains",
     "gym_mpc_box_lanes_workspace", "gym_mpc_box_lanes_rollout", "gym_mpc_box_lanes_rollout_fallback",
     "gym_timing_create", "gym_timing_destroy", "gym_timing_collect",
+    "gym_lqr_lanes_rollout_plant", "gym_mpc_box_lanes_rollout_plant",
 )
 KERNEL_KINDS = ("backward", "trial", "candidates", "retry", "stats", "phase_odd", "phase_even", "sigma", "run",
                 "tail")
@@ -91,6 +92,7 @@ _MP, _WP, _AP, _BP = C.POINTER(GymModel), C.POINTER(GymWeights), C.POINTER(GymAr
 _SIGS = {
     "gym_abi_version": [],
     "gym_model_from_params": [_P, _D, _MP],
+    "gym_models_from_params": [_P, _I64, _D, _P],
     "gym_continuous_dynamics": [_MP, _P, _P, _P, _I64, _P],
     "gym_rk4_step": [_MP, _P, _P, _P, _I64, _P],
     "gym_jacobians": [_MP, _P, _P, _P, _P, _I64, _P],
@@ -145,6 +147,9 @@ _SIGS = {
                                   _P, _P, _P],
     "gym_mpc_box_lanes_rollout_fallback": [_MP, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _D, _I32, _I32, _P, _I64,
                                            _P, _P, _P, _P, _P, _P],
+    "gym_lqr_lanes_rollout_plant": [_MP, _P, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P, _P],
+    "gym_mpc_box_lanes_rollout_plant": [_MP, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _D, _I32, _I32, _P,
+                                        _I64, _P, _P, _P, _P, _P, _P],
     "gym_timing_create": [C.POINTER(GymTiming)],
     "gym_timing_destroy": [C.POINTER(GymTiming)],
     "gym_timing_collect": [C.POINTER(GymTiming)],

@@ -409,6 +409,21 @@ int gym_model_from_params(const double p[11], double dt, gym_model* out) {
     return 0;
 }
 
+// n parameter sets (n,11) -> n models, each gym_model_from_params' own; refused unless every entry is finite and the
+// mass matrix is positive definite at every theta2: d > 0 and d (a - d) > b^2, gym::accel's denominator dad - bb cos^2
+int gym_models_from_params(const double* params, int64_t n, double dt, gym_model* out) {
+    if (!params || !out || n < 1) return GYM_EINVAL;
+    for (int64_t i = 0; i < n; ++i) {
+        const double* p = params + 11 * i;
+        for (int j = 0; j < 11; ++j)
+            if (!(p[j] - p[j] == 0.0)) return GYM_EINVAL;   // inf - inf and NaN - NaN are NaN
+        gym_model* o = out + i;
+        gym_model_from_params(p, dt, o);
+        if (!(o->d > 0.0 && o->d * (o->a - o->d) > o->b * o->b)) return GYM_EINVAL;
+    }
+    return 0;
+}
+
 static int point_op(const gym_model* m, const double* x, const double* u, double* o1, double* o2, int64_t n, void* s,
                     int what) {
     if (!m || !x || !u || !o1 || n < 0 || (what == 2 && !o2)) return GYM_EINVAL;

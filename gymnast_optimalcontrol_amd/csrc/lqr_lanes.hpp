@@ -206,6 +206,20 @@ __device__ __forceinline__ double lqr_lane_feedback(double2 ka, double2 kb, doub
     return f1 + (((ka.x * d0 + ka.y * d1) + kb.x * d2) + kb.y * d3);
 }
 
+// The model of a closed loop's plant step x_{t+1} = RK4(x_t, u_t).  Without a table it is the design
+// model m itself, by reference, so a kernel instantiated without one is the kernel it was before tables existed.  With
+// one it is row `row` of a (B,P) table of gym_model (64 bytes a row, 16-byte aligned, read once per thread before the
+// time loop), made a Dyn by the constructor the host uses for m, so bb, dad, h2 and h6 are the same single-rounded
+// operations on both sides; dt is the design model's.  A thread that is not `valid` (padding) reads nothing and gets
+// the design model.  The nine coefficients are then per-thread registers, not scalars.
+__device__ __forceinline__ const Dyn& lane_plant(const Dyn& m, int64_t, bool) { return m; }
+__device__ __forceinline__ Dyn lane_plant(const Dyn& m, int64_t row, bool valid, const gym_model* rows) {
+    if (!valid) return m;
+    const double2* r = reinterpret_cast<const double2*>(rows + row);
+    const double2 ab = r[0], dg = r[1], gf = r[2], fd = r[3];
+    return Dyn(gym_model{ab.x, ab.y, dg.x, dg.y, gf.x, gf.y, fd.x, m.h});
+}
+
 // simulate_tracking per lane and perturbed start: B P threads, a wavefront = 64 consecutive lanes at one start index
 // p, so its reads of x_opt, u_opt and K1 are the gain sweep's coalesced rows.  The P wavefronts of one lane group are
 // dealt to the same XCD (workgroups go round-robin over the 8 XCDs; gridDim.x is a multiple of 8) and run back to
@@ -218,8 +232,11 @@ __device__ __forceinline__ double lqr_lane_feedback(double2 ka, double2 kb, doub
 // k_track_rollout_pair does for its few hundred wavefronts, reach rows 16 KB apart and were 3.3x (non-temporal) and
 // 1.5x (plain) slower at 262,144 lanes; 4 staged steps were 2-17 % slower than 8.  Padding lanes of a
 // ragged group run on their zero trajectory (the staging is a whole-wavefront step) and write nothing.
-template <bool TRAJ>
-__global__ __launch_bounds__(BLK) void k_lqr_lane_rollout(Dyn m, const double* __restrict__ x0,
+// k<TRAJ>: plant and design model are one; k<TRAJ, const gym_model*>: the pack Pl is the one parameter after m, the
+// (B,P) table whose row l P + p closed loop (l, p) integrates (lane_plant).  The feedback, the streams and m.h stay
+// the design model's.
+template <bool TRAJ, class... Pl>
+__global__ __launch_bounds__(BLK) void k_lqr_lane_rollout(Dyn m, Pl... plant, const double* __restrict__ x0,
                                                           const double2* __restrict__ xs, const double* __restrict__ us,
                                                           const double2* __restrict__ ks, int64_t B, int64_t Bp, int P,
                                                           int N, double* __restrict__ xo, double* __restrict__ uo,
@@ -237,6 +254,7 @@ __global__ __launch_bounds__(BLK) void k_lqr_lane_rollout(Dyn m, const double* _
     if (!TRAJ && !valid) return;
     const int T = N - 1;
     const int64_t row = l * P + p;
+    decltype(auto) pm = lane_plant(m, row, valid, plant...);   // padding lanes of a ragged group: the design model
     double2* xl = reinterpret_cast<double2*>(xo + 4 * (int64_t)N * row);
     double n0 = 0.0, n1 = 0.0, n2 = 0.0, n3 = 0.0;
     if (valid) {
@@ -267,7 +285,7 @@ __global__ __launch_bounds__(BLK) void k_lqr_lane_rollout(Dyn m, const double* _
         f1 = us[pix(tn, 1, 2, l, Bp)];
         emax = gym::nanmax_abs(gym::nanmax_abs(gym::nanmax_abs(gym::nanmax_abs(emax, d0), d1), d2), d3);
         umax = gym::nanmax_abs(umax, v1);
-        gym::rk4(m, n0, n1, n2, n3, v1, pk);
+        gym::rk4(pm, n0, n1, n2, n3, v1, pk);
         if (TRAJ) {
             const int s = t % S;
             stage[(0 * S + s) * LL_PITCH + ln] = n0;

@@ -61,14 +61,31 @@ __device__ __forceinline__ void box_lane_row(const Dyn& m, const double2* __rest
     dst[20] = uu.x; dst[21] = uu.y;
 }
 
+// k_mpc_box_lane_rollout's optional parameters after max_it, the pack Ex = [int fb_it] [const gym_model* plant]: the
+// fallback's iteration cap (0 without it: box_qp_lane's default, never read) and the plant's model (lane_plant)
+__device__ __forceinline__ int box_ex_fb_it() { return 0; }
+__device__ __forceinline__ int box_ex_fb_it(const gym_model*) { return 0; }
+template <class... Pl> __device__ __forceinline__ int box_ex_fb_it(int fb_it, Pl...) { return fb_it; }
+template <class... Pl>
+__device__ __forceinline__ decltype(auto) box_ex_plant(const Dyn& m, int64_t row, bool valid, Pl... plant) {
+    return lane_plant(m, row, valid, plant...);
+}
+template <class... Pl>
+__device__ __forceinline__ decltype(auto) box_ex_plant(const Dyn& m, int64_t row, bool valid, int, Pl... plant) {
+    return lane_plant(m, row, valid, plant...);
+}
+
 // x0 (B,P,4); lane-major x_opt (B,N,4), u_opt (B,N-1,2).  Outputs lane-major: xo (B,P,N,4), uo (B,P,N-1,2) (both or
 // neither), summary (3,B,P) = err_final, err_max, u_max as k_lqr_lane_rollout, it_out (B,P,N-1) or null, unconv_out
 // (B,P).  grid B nblk (nblk = ceil(P / 64)), 64 threads; LDS dynamic: (kBoxRow + 4) (L - 1) doubles.
 // <false>: the active set alone; <true, int>: fb_it after max_it, handed to box_qp_lane's projected-Newton fallback
 // (qp_iters then counts both phases, unconverged only the QPs that neither phase finished), as mpc_box.hpp's kernels.
-template <bool FB, class... Fb>
+// <FB, [int,] const gym_model*>: a mismatched plant, the (B,P) table last in the pack; closed loop (b, p) integrates
+// its row b P + p (lane_plant, lqr_lanes.hpp).  The linearisation, the windows, the QP and m.h stay the
+// design model's.
+template <bool FB, class... Ex>
 __global__ __launch_bounds__(64) void k_mpc_box_lane_rollout(Dyn m, M44 Q, double r, const double* __restrict__ QT,
-                                                             double tau, int max_it, Fb... fb_it,
+                                                             double tau, int max_it, Ex... ex,
                                                              const double2* __restrict__ x_opt,
                                                              const double2* __restrict__ u_opt,
                                                              const double* __restrict__ x0, int P, int N, int L,
@@ -87,6 +104,7 @@ __global__ __launch_bounds__(64) void k_mpc_box_lane_rollout(Dyn m, M44 Q, doubl
     const bool valid = p < P;
     const int64_t row = b * P + (valid ? p : 0);
     const int64_t BP = (int64_t)gridDim.x / nblk * P;
+    decltype(auto) pm = box_ex_plant(m, row, valid, ex...);   // a block's padding threads (p >= P): the design model
     const double2* xlo = x_opt + 2 * (b * N);
     const double2* ulo = u_opt + b * T;
     const BoxWs ws{wsd + b * ((int64_t)kBoxSlots * Lm + 4) * P, wst + b * Lm * P, P, p};
@@ -134,13 +152,14 @@ __global__ __launch_bounds__(64) void k_mpc_box_lane_rollout(Dyn m, M44 Q, doubl
         double u1;
         int iters;
         bool conv;
-        box_qp_lane<false, FB>(w, Lm, Q, r, QT, tau, max_it, ws, valid, d0, d1, d2, d3, u1, iters, conv, fb_it...);
+        box_qp_lane<false, FB>(w, Lm, Q, r, QT, tau, max_it, ws, valid, d0, d1, d2, d3, u1, iters, conv,
+                               box_ex_fb_it(ex...));
         if (valid) {
             const double v0 = box_apply(f[0], box_clip0(f[0], tau), tau), v1 = box_apply(f[1], u1, tau);
             emax = gym::nanmax_abs(gym::nanmax_abs(gym::nanmax_abs(gym::nanmax_abs(emax, d0), d1), d2), d3);
             umax = gym::nanmax_abs(umax, v1);
             unconv += conv ? 0 : 1;
-            gym::rk4(m, n0, n1, n2, n3, v1, pk);
+            gym::rk4(pm, n0, n1, n2, n3, v1, pk);
             if (it_out) it_out[(int64_t)T * row + s] = iters;
             if (xo) {
                 ul[s] = make_double2(v0, v1);

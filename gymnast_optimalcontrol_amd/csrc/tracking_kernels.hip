@@ -55,6 +55,8 @@ inline bool lanes_sizes_ok(int64_t B, int32_t N) { return B >= 1 && N >= 2 && (B
 inline bool box_lanes_sizes_ok(int64_t B, int32_t P, int32_t N, int32_t L) {
     return B >= 1 && P >= 1 && N >= 2 && window_ok(L) && B <= GYM_MAX_BP / P;
 }
+// a plant table: its 64-byte rows are read with 16-byte loads
+inline bool plant_ok(const gym_model* plant) { return plant && reinterpret_cast<uintptr_t>(plant) % 16 == 0; }
 
 template <bool ALL>   // K_out: every gain of every window (ALL) or each window's first gain
 int mpc_gains_launch(const gym_model* m, const double* x_ref, const double* u_ref, int32_t S, const double* x_f,
@@ -294,19 +296,41 @@ int gym_lqr_lanes_gains(const gym_model* m, const double* x_opt, const double* u
     return launch_status();
 }
 
-// simulate_tracking (trajectory_tracking.py:206-216) per lane and perturbed start
-int gym_lqr_lanes_rollout(const gym_model* m, const double* x0, int64_t B, int32_t P, int32_t N, const void* ws,
-                          int64_t ws_bytes, double* x_out, double* u_out, double* summary_out, void* s) {
+// simulate_tracking (trajectory_tracking.py:206-216) per lane and perturbed start; plant: the (B,P) table of the
+// mismatched-plant kernels, or null for the design model itself
+static int lanes_rollout_launch(const gym_model* m, const gym_model* plant, const double* x0, int64_t B, int32_t P,
+                                int32_t N, const void* ws, int64_t ws_bytes, double* x_out, double* u_out,
+                                double* summary_out, void* s) {
     if (!m || !x0 || !ws || !summary_out || !lanes_sizes_ok(B, N) || P < 1 || B > GYM_MAX_BP / P ||
         (x_out == nullptr) != (u_out == nullptr))
         return GYM_EINVAL;
     const LanesWs w = lanes_ws(const_cast<void*>(ws), B, N);   // read only: the kernels take it as const
     if (ws_bytes < w.lo.bytes) return GYM_EINVAL;
     const int64_t nb = w.groups * P;                       // <= 2^20 + 2^26 / 64: far below the grid limit
-    hipLaunchKernelGGL(x_out ? k_lqr_lane_rollout<true> : k_lqr_lane_rollout<false>, dim3((unsigned)((nb + 7) / 8 * 8)),
-                       dim3(BLK), 0, (hipStream_t)s, Dyn(*m), x0, w.xs, w.us, w.ks, B, w.lo.Bp, (int)P, (int)N, x_out,
-                       u_out, summary_out);
+    const dim3 grid((unsigned)((nb + 7) / 8 * 8));
+    if (plant)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(x_out ? k_lqr_lane_rollout<true, const gym_model*>
+                                                 : k_lqr_lane_rollout<false, const gym_model*>),
+                           grid, dim3(BLK), 0, (hipStream_t)s, Dyn(*m), plant, x0, w.xs, w.us, w.ks, B, w.lo.Bp, (int)P,
+                           (int)N, x_out, u_out, summary_out);
+    else
+        hipLaunchKernelGGL(x_out ? k_lqr_lane_rollout<true> : k_lqr_lane_rollout<false>, grid, dim3(BLK), 0,
+                           (hipStream_t)s, Dyn(*m), x0, w.xs, w.us, w.ks, B, w.lo.Bp, (int)P, (int)N, x_out, u_out,
+                           summary_out);
     return launch_status();
+}
+
+int gym_lqr_lanes_rollout(const gym_model* m, const double* x0, int64_t B, int32_t P, int32_t N, const void* ws,
+                          int64_t ws_bytes, double* x_out, double* u_out, double* summary_out, void* s) {
+    return lanes_rollout_launch(m, nullptr, x0, B, P, N, ws, ws_bytes, x_out, u_out, summary_out, s);
+}
+
+// simulate_tracking (:206-216) with the plant step of closed loop (b, p) on plant[b][p] (dynamics.py:15-61)
+int gym_lqr_lanes_rollout_plant(const gym_model* m, const gym_model* plant, const double* x0, int64_t B, int32_t P,
+                                int32_t N, const void* ws, int64_t ws_bytes, double* x_out, double* u_out,
+                                double* summary_out, void* s) {
+    if (!plant_ok(plant)) return GYM_EINVAL;
+    return lanes_rollout_launch(m, plant, x0, B, P, N, ws, ws_bytes, x_out, u_out, summary_out, s);
 }
 
 // ---- per-lane MPC tracking (mpc_lanes.hpp) ----
@@ -339,11 +363,12 @@ int gym_mpc_box_lanes_workspace(int64_t B, int32_t P, int32_t L, int64_t* bytes_
 }
 
 // solve_mpc_tracking's closed loop (trajectory_tracking.py:43-67) with solver_mpc's test_constraints (:87-114) per lane
-static int box_lanes_launch(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0, int64_t B,
-                            int32_t P, int32_t N, int32_t L, const double Q[16], const double R[4],
-                            const double* QT_dev, double tau_max, int32_t max_qp_iters, int32_t fallback_iters,
-                            void* ws, int64_t ws_bytes, double* x_out, double* u_out, double* summary_out,
-                            int32_t* qp_iters_out, int32_t* unconverged_out, void* s) {
+// plant: the (B,P) table of the mismatched-plant kernels, or null for the design model itself
+static int box_lanes_launch(const gym_model* m, const gym_model* plant, const double* x_opt, const double* u_opt,
+                            const double* x0, int64_t B, int32_t P, int32_t N, int32_t L, const double Q[16],
+                            const double R[4], const double* QT_dev, double tau_max, int32_t max_qp_iters,
+                            int32_t fallback_iters, void* ws, int64_t ws_bytes, double* x_out, double* u_out,
+                            double* summary_out, int32_t* qp_iters_out, int32_t* unconverged_out, void* s) {
     if (!m || !x_opt || !u_opt || !x0 || !Q || !R || !QT_dev || !ws || !summary_out || !unconverged_out ||
         !box_lanes_sizes_ok(B, P, N, L) || !finite_pos(tau_max) || max_qp_iters < 1 || !box_weights_ok(R) ||
         !lanes_sym(Q) || (x_out == nullptr) != (u_out == nullptr))
@@ -354,7 +379,17 @@ static int box_lanes_launch(const gym_model* m, const double* x_opt, const doubl
     const size_t lds = sizeof(double) * (kBoxRow + 4) * (L - 1);
     const dim3 grid((unsigned)(B * nblk));
     const double2 *xo2 = reinterpret_cast<const double2*>(x_opt), *uo2 = reinterpret_cast<const double2*>(u_opt);
-    if (fallback_iters)
+    if (plant && fallback_iters)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mpc_box_lane_rollout<true, int, const gym_model*>), grid, dim3(64), lds,
+                           (hipStream_t)s, Dyn(*m), m44(Q), R[3], QT_dev, tau_max, max_qp_iters, fallback_iters, plant,
+                           xo2, uo2, x0, (int)P, (int)N, (int)L, nblk, ws_at<double>(ws, 0),
+                           ws_at<int32_t>(ws, lo.off_st), x_out, u_out, summary_out, qp_iters_out, unconverged_out);
+    else if (plant)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mpc_box_lane_rollout<false, const gym_model*>), grid, dim3(64), lds,
+                           (hipStream_t)s, Dyn(*m), m44(Q), R[3], QT_dev, tau_max, max_qp_iters, plant, xo2, uo2, x0,
+                           (int)P, (int)N, (int)L, nblk, ws_at<double>(ws, 0), ws_at<int32_t>(ws, lo.off_st), x_out,
+                           u_out, summary_out, qp_iters_out, unconverged_out);
+    else if (fallback_iters)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mpc_box_lane_rollout<true, int>), grid, dim3(64), lds, (hipStream_t)s,
                            Dyn(*m), m44(Q), R[3], QT_dev, tau_max, max_qp_iters, fallback_iters, xo2, uo2, x0, (int)P,
                            (int)N, (int)L, nblk, ws_at<double>(ws, 0), ws_at<int32_t>(ws, lo.off_st), x_out, u_out,
@@ -372,8 +407,8 @@ int gym_mpc_box_lanes_rollout(const gym_model* m, const double* x_opt, const dou
                               const double* QT_dev, double tau_max, int32_t max_qp_iters, void* ws, int64_t ws_bytes,
                               double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
                               int32_t* unconverged_out, void* s) {
-    return box_lanes_launch(m, x_opt, u_opt, x0, B, P, N, L, Q, R, QT_dev, tau_max, max_qp_iters, 0, ws, ws_bytes,
-                            x_out, u_out, summary_out, qp_iters_out, unconverged_out, s);
+    return box_lanes_launch(m, nullptr, x_opt, u_opt, x0, B, P, N, L, Q, R, QT_dev, tau_max, max_qp_iters, 0, ws,
+                            ws_bytes, x_out, u_out, summary_out, qp_iters_out, unconverged_out, s);
 }
 
 int gym_mpc_box_lanes_rollout_fallback(const gym_model* m, const double* x_opt, const double* u_opt, const double* x0,
@@ -383,8 +418,21 @@ int gym_mpc_box_lanes_rollout_fallback(const gym_model* m, const double* x_opt, 
                                        double* u_out, double* summary_out, int32_t* qp_iters_out,
                                        int32_t* unconverged_out, void* s) {
     if (fallback_iters < 1) return GYM_EINVAL;
-    return box_lanes_launch(m, x_opt, u_opt, x0, B, P, N, L, Q, R, QT_dev, tau_max, max_qp_iters, fallback_iters, ws,
-                            ws_bytes, x_out, u_out, summary_out, qp_iters_out, unconverged_out, s);
+    return box_lanes_launch(m, nullptr, x_opt, u_opt, x0, B, P, N, L, Q, R, QT_dev, tau_max, max_qp_iters,
+                            fallback_iters, ws, ws_bytes, x_out, u_out, summary_out, qp_iters_out, unconverged_out, s);
+}
+
+// the closed loop (trajectory_tracking.py:43-67) with the plant step of (b, p) on plant[b][p] (dynamics.py:15-61);
+// fallback_iters = 0: the active set alone
+int gym_mpc_box_lanes_rollout_plant(const gym_model* m, const gym_model* plant, const double* x_opt,
+                                    const double* u_opt, const double* x0, int64_t B, int32_t P, int32_t N, int32_t L,
+                                    const double Q[16], const double R[4], const double* QT_dev, double tau_max,
+                                    int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes,
+                                    double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
+                                    int32_t* unconverged_out, void* s) {
+    if (!plant_ok(plant) || fallback_iters < 0) return GYM_EINVAL;
+    return box_lanes_launch(m, plant, x_opt, u_opt, x0, B, P, N, L, Q, R, QT_dev, tau_max, max_qp_iters,
+                            fallback_iters, ws, ws_bytes, x_out, u_out, summary_out, qp_iters_out, unconverged_out, s);
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .params import PARAM_SETS, DT, Q_DIAG, R_DIAG, QT_DIAG
+from .params import PARAM_NAMES, PARAM_SETS, DT, Q_DIAG, R_DIAG, QT_DIAG
 
 F64, I32, U8 = torch.float64, torch.int32, torch.uint8
 
@@ -75,7 +75,27 @@ class Weights:
         return Weights(*out)
 
 
-class AcrobotEngine:
+class PlantTables:
+    """The plant tables of the per-lane trackers (AcrobotEngine's base: the engine's own attributes stay its
+    launchers, one per ABI entry point with a stream; this one is a host call and an upload)."""
+
+    def plant_table(self, plant, B: int, P: int) -> torch.Tensor:
+        """The (B,P,8) float64 device table of a mismatched plant, rows in gym_model's field order (a, b, d, g1, g2,
+        f1, f2, dt), that lqr_lanes_rollout / mpc_box_lanes_rollout take as ``plant``: check_plant's (B,P,11)
+        parameters, reduced by gym_models_from_params with the engine's dt (row i bit for bit gym_model_from_params'),
+        then one upload.  ValueError: check_plant's, and a set whose mass matrix is not positive definite."""
+        par = np.ascontiguousarray(check_plant(plant, B, P, self.params).reshape(B * P, 11))
+        rows = np.empty((B * P, 8))
+        try:
+            self._call("gym_models_from_params", par, B * P, self.dt, rows, stream=False)
+        except RuntimeError as e:          # the entries are finite (check_plant), so GYM_EINVAL is the other refusal
+            raise ValueError("plant: a parameter set's mass matrix is not positive definite for every theta2 (it "
+                             "needs d > 0 and d (a - d) > b^2 with a = I1 + I2 + lc1^2 m1 + m2 (l1^2 + lc2^2), "
+                             "b = m2 l1 lc2, d = I2 + lc2^2 m2)") from e
+        return torch.as_tensor(rows.reshape(B, P, 8), device=self.device)
+
+
+class AcrobotEngine(PlantTables):
     """Launchers for one acrobot parameter set on one HIP device."""
 
     def __init__(self, params=1, dt: float = DT, weights: Weights | None = None, device=None,
@@ -519,16 +539,23 @@ class AcrobotEngine:
         self._call("gym_lqr_lanes_gains", self.model, x_opt, u_opt, B, N, Qh, Rh, QTh, ws, ws_bytes, K)
         return ws, K
 
-    def lqr_lanes_rollout(self, ws, x0, N: int, trajectories: bool = True):
+    def lqr_lanes_rollout(self, ws, x0, N: int, trajectories: bool = True, plant=None):
         """gym_lqr_lanes_rollout on a workspace lqr_lanes_gains filled: x0 (B,P,4) -> (x (B,P,N,4), u (B,P,N-1,2),
-        summary (3,B,P) = err_final, err_max, u_max) on the device; x, u are None unless ``trajectories``."""
+        summary (3,B,P) = err_final, err_max, u_max) on the device; x, u are None unless ``trajectories``.
+        ``plant``: a plant_table (B,P,8); closed loop (b, p) then integrates its own plant
+        (gym_lqr_lanes_rollout_plant), the controller staying on this engine's model."""
         x0 = self.t(x0)
         check_lane_starts(x0)
         B, P, N = x0.shape[0], x0.shape[1], int(N)
         ws, ws_bytes = self._workspace(ws)
+        if plant is not None:
+            check_plant_table(plant, B, P)
         x, u = self._buf(B, P, N, 4, want=trajectories), self._buf(B, P, N - 1, 2, want=trajectories)
         summary = self._buf(3, B, P)
-        self._call("gym_lqr_lanes_rollout", self.model, x0, B, P, N, ws, ws_bytes, x, u, summary)
+        if plant is None:
+            self._call("gym_lqr_lanes_rollout", self.model, x0, B, P, N, ws, ws_bytes, x, u, summary)
+        else:
+            self._call("gym_lqr_lanes_rollout_plant", self.model, plant, x0, B, P, N, ws, ws_bytes, x, u, summary)
         return x, u, summary
 
     # ------------------------------------------------------------- per-lane MPC tracking
@@ -556,7 +583,8 @@ class AcrobotEngine:
         return self._ws_bytes("gym_mpc_box_lanes_workspace", B, P, L)
 
     def mpc_box_lanes_rollout(self, x_opt, u_opt, x0, Q, R, QT, L: int, tau_max: float, max_qp_iters: int = 32,
-                              trajectories: bool = True, max_ws_bytes: int | None = None, fallback_iters: int = 0):
+                              trajectories: bool = True, max_ws_bytes: int | None = None, plant=None,
+                              fallback_iters: int = 0):
         """gym_mpc_box_lanes_rollout: the torque-limited MPC closed loop of every lane along its own x_opt (B,N,4),
         u_opt (B,N-1,2) from the starts x0 (B,P,4); QT (4,4) a device tensor as in mpc_lanes_gains.  Returns device
         tensors (x (B,P,N,4), u (B,P,N-1,2), summary (3,B,P), qp_iters (B,P,N-1) int32, unconverged (B,P) int32); x, u
@@ -564,13 +592,18 @@ class AcrobotEngine:
         allocated here; a batch whose workspace would exceed ``max_ws_bytes`` (default: BOX_LANES_WS_SHARE of the free
         device memory) runs in chunks of whole lanes, one call each -- the same results, lanes being independent.
         ``fallback_iters`` > 0 (gym_mpc_box_lanes_rollout_fallback, every chunk): qp_iters counts active-set sweeps
-        plus Newton iterations and unconverged only the QPs that neither phase finished."""
+        plus Newton iterations and unconverged only the QPs that neither phase finished.  ``plant``: a plant_table
+        (B,P,8); closed loop (b, p) then integrates its own plant (gym_mpc_box_lanes_rollout_plant, with or without
+        the fallback; the table is sliced with the other lane-major buffers), the controller staying on this engine's
+        model."""
         x_opt = self.t(x_opt); u_opt = self.t(u_opt); x0 = self.t(x0)
         B, N = check_lane_trajectories(x_opt, u_opt)
         check_lane_starts(x0, B)
         P, L = x0.shape[1], check_window(L, "the torque-limited QP")
         if B * P > _lib.MAX_BP:
             raise ValueError(f"{B} lanes x {P} starts exceed {_lib.MAX_BP} closed loops per call")
+        if plant is not None:
+            check_plant_table(plant, B, P)
         check_box(tau_max, max_qp_iters, fallback_iters)
         fb = int(fallback_iters)
         Rh = check_diagonal_R(R, "the torque-limited QP")
@@ -588,9 +621,14 @@ class AcrobotEngine:
             b1 = min(B, b0 + chunk)
             part = lambda a: None if a is None else a[b0:b1]  # noqa: E731 -- this chunk's lanes of a lane-major buffer
             sm = summary if chunk >= B else self._buf(3, b1 - b0, P)
-            self._call(*_with_fallback("gym_mpc_box_lanes_rollout", fb, self.model, part(x_opt), part(u_opt), part(x0),
-                                       b1 - b0, P, N, L, Qh, Rh, QTd, float(tau_max), int(max_qp_iters)),
-                       ws, ws.numel(), part(x), part(u), sm, part(it), part(unconv))
+            sizes = (b1 - b0, P, N, L, Qh, Rh, QTd, float(tau_max), int(max_qp_iters))
+            if plant is None:
+                head = _with_fallback("gym_mpc_box_lanes_rollout", fb, self.model, part(x_opt), part(u_opt), part(x0),
+                                      *sizes)
+            else:                                      # one entry point for both: fallback_iters 0 = the active set
+                head = ("gym_mpc_box_lanes_rollout_plant", self.model, part(plant), part(x_opt), part(u_opt), part(x0),
+                        *sizes, fb)
+            self._call(*head, ws, ws.numel(), part(x), part(u), sm, part(it), part(unconv))
             if sm is not summary:
                 summary[:, b0:b1] = sm
         return x, u, summary, it, unconv
@@ -703,6 +741,56 @@ def _with_fallback(name, fb, *head):
     """The call list up to max_qp_iters: the entry point itself, or with fb > 0 its ..._fallback twin, which takes
     fallback_iters right after max_qp_iters."""
     return (name + "_fallback",) + head + (fb,) if fb else (name,) + head
+
+
+def check_plant(plant, B: int, P: int, own_params) -> np.ndarray:
+    """The parameters of every closed loop's plant, (B,P,11) float64 in params.PARAM_NAMES order, from any of
+      * a set number 1-3 (params.PARAM_SETS);
+      * a dict of parameter names to scalars or arrays broadcastable to (B,P); names it leaves out are taken from
+        ``own_params`` (the engine's own set), so {} is the design model itself;
+      * an array (11,), (P,11) per start, (B,11) or (B,1,11) per lane, or (B,P,11).  NumPy's broadcasting reads a
+        2-D array as per start, so (n,11) is per lane only where n = B != P (always with an x0 that came as (B,4),
+        where P is 1); (B,1,11) says per lane for any P.
+    ValueError, in these words: "unknown plant parameter" for a name not in PARAM_NAMES, "plant set" for a number
+    that is no set, "plant rows must hold 11 parameters" for a wrong trailing size, "does not broadcast" for a shape
+    that fits none of the forms, "must be finite" for a NaN or inf anywhere."""
+    B, P = int(B), int(P)
+    if isinstance(plant, (int, np.integer)) and not isinstance(plant, bool):
+        if int(plant) not in PARAM_SETS:
+            raise ValueError(f"plant set must be one of {sorted(PARAM_SETS)}, got {plant}")
+        plant = dict(PARAM_SETS[int(plant)])
+    if isinstance(plant, dict):
+        unknown = [k for k in plant if k not in PARAM_NAMES]
+        if unknown:
+            raise ValueError(f"unknown plant parameter {unknown[0]!r}: the names are {', '.join(PARAM_NAMES)}")
+        out = np.empty((B, P, 11))
+        for j, name in enumerate(PARAM_NAMES):
+            v = np.asarray(plant.get(name, own_params[name]), dtype=np.float64)
+            try:
+                out[:, :, j] = np.broadcast_to(v, (B, P))
+            except ValueError:
+                raise ValueError(f"plant[{name!r}] {v.shape} does not broadcast to ({B},{P})") from None
+    else:
+        a = np.asarray(plant.detach().cpu() if isinstance(plant, torch.Tensor) else plant, dtype=np.float64)
+        if a.ndim < 1 or a.shape[-1] != 11:
+            raise ValueError(f"plant rows must hold 11 parameters ({', '.join(PARAM_NAMES)}), got {a.shape}")
+        if a.ndim == 2 and a.shape[0] == B != P:
+            a = a[:, None, :]                          # (B,11): per lane
+        try:
+            out = np.broadcast_to(a, (B, P, 11))
+        except ValueError:
+            raise ValueError(f"plant {a.shape} does not broadcast to ({B},{P},11): give (11,), ({P},11), ({B},11), "
+                             f"({B},1,11) or ({B},{P},11)") from None
+    if not np.isfinite(out).all():
+        raise ValueError("plant parameters must be finite")
+    return out
+
+
+def check_plant_table(table, B: int, P: int):
+    """A plant table as AcrobotEngine.plant_table makes it: a float64 tensor (B,P,8), one gym_model per closed loop."""
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float64 or tuple(table.shape) != (B, P, 8):
+        raise ValueError(f"plant must be a plant_table ({B},{P},8) float64 tensor, got "
+                         f"{getattr(table, 'dtype', type(table).__name__)} {tuple(getattr(table, 'shape', ()))}")
 
 
 def check_device_QT(QT):

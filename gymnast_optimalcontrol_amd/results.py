@@ -72,14 +72,16 @@ class SolveResult:
     def track_lqr(self, x0=None, dx0=None, **kw):
         """LQR tracking of every lane's own result (trajectory_tracking.LQR_tracking_lanes on this result's x, u):
         x0 (B,4) or (B,P,4) perturbed starts, default x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4) (default: no
-        perturbation).  Keyword arguments go to LQR_tracking_lanes.  Returns its LqrLanesResult."""
+        perturbation).  Keyword arguments go to LQR_tracking_lanes, ``plant=`` among them: a mismatched plant per closed
+        loop, e.g. ``plant=trajectory_tracking.sample_plants(B, P)`` for dx0 (B,P,4).  Returns its LqrLanesResult."""
         from . import trajectory_tracking as tt
         return tt.LQR_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
 
     def track_mpc(self, x0=None, dx0=None, **kw):
         """Receding-horizon MPC tracking of every lane's own result (trajectory_tracking.MPC_tracking_lanes on this
         result's x, u); x0 / dx0 as track_lqr.  Keyword arguments (T_pred, Q, R, trajectories, gains, tau_max,
-        max_qp_iters) go to MPC_tracking_lanes.  Returns its MpcLanesResult; with a torque limit (``tau_max=18`` is the
+        max_qp_iters, plant) go to MPC_tracking_lanes; ``plant=`` simulates a mismatched plant per closed loop, with
+        and without a torque limit.  Returns its MpcLanesResult; with a torque limit (``tau_max=18`` is the
         reference's) every lane's closed loop keeps |u| <= tau_max and the result is an MpcBoxLanesResult.
         ``tau_max=trajectory_tracking.TorqueLimit(18.0)`` adds the projected-Newton fallback: a QP whose active set
         has not settled after max_qp_iters sweeps is finished by it, qp_iters counts both phases and unconverged only

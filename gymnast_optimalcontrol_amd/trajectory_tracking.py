@@ -28,7 +28,10 @@ gym_lqr_lanes_rollout).  ``MPC_tracking_lanes`` / ``mpc_gains_lanes`
 MPC (no torque limit): the first gain of every T_pred-stage window along every lane's own trajectory in the kernel of
 csrc/mpc_lanes.hpp (gym_mpc_lanes_gains), then the same closed-loop rollout; with ``tau_max`` every
 closed loop solves its own torque-limited QPs along its own lane's trajectory in the kernel of csrc/mpc_box_lanes.hpp
-(gym_mpc_box_lanes_rollout).  There is no CPU fallback.
+(gym_mpc_box_lanes_rollout).  ``plant=`` on both simulates a mismatched plant per closed loop: the
+controller stays on the design model and the RK4 step of closed loop (b, p) runs on its own parameter set
+(gym_lqr_lanes_rollout_plant / gym_mpc_box_lanes_rollout_plant); ``sample_plants`` draws such sets.
+There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -39,7 +42,8 @@ import torch
 
 from . import _lib
 from . import dynamics as _dyn
-from .engine import check_box, check_lane_starts, check_lane_trajectories, check_window
+from .engine import check_box, check_lane_starts, check_lane_trajectories, check_plant, check_window
+from .params import PARAM_NAMES, PARAM_SETS
 from .dynamics import dt, ns, ni  # noqa: F401  (the reference module's namespace, trajectory_tracking.py:3)
 
 nu = ni
@@ -196,9 +200,25 @@ def _drop_starts_axis(flat, summary, *per_start):
     return (summary[:, :, 0], *(None if t is None else t[:, 0] for t in per_start))
 
 
-def _lane_rollout(eng, ws, x0, N, trajectories, flat):
-    """The closed loop of x0 (B,P,4) on a workspace a per-lane gains call filled (gym_lqr_lanes_rollout)."""
-    x, u, s = eng.lqr_lanes_rollout(ws, x0, N, trajectories=trajectories)
+def _plant_kw(eng, plant, x0) -> dict:
+    """The engine keyword of a mismatched plant for the starts x0 (B,P,4): its device table; none without one, so a
+    call without ``plant`` is the call it always was."""
+    return {} if plant is None else {"plant": eng.plant_table(plant, x0.shape[0], x0.shape[1])}
+
+
+def _check_plant(plant, x_opt, x0):
+    """``plant=`` refused before any device is needed (engine.check_plant on the caller's own shapes; the parameters
+    a dict leaves out are those of the set dynamics.engine() runs on).  Malformed x_opt / x0 are left to their own
+    checks."""
+    xs, ss = tuple(np.shape(x_opt)), tuple(np.shape(x0))
+    if plant is not None and len(xs) == 3 and len(ss) in (2, 3):
+        check_plant(plant, xs[0], 1 if len(ss) == 2 else ss[1], PARAM_SETS[_dyn._pset])
+
+
+def _lane_rollout(eng, ws, x0, N, trajectories, flat, plant=None):
+    """The closed loop of x0 (B,P,4) on a workspace a per-lane gains call filled (gym_lqr_lanes_rollout; with
+    ``plant`` gym_lqr_lanes_rollout_plant)."""
+    x, u, s = eng.lqr_lanes_rollout(ws, x0, N, trajectories=trajectories, **_plant_kw(eng, plant, x0))
     s, x, u = _drop_starts_axis(flat, s, x, u)
     return x, u, s
 
@@ -211,18 +231,44 @@ def lqr_gains_lanes(x_opt, u_opt, Q=Q_REG, R=R_REG, QT=QT_REG) -> torch.Tensor:
     return eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=True)[1]
 
 
-def LQR_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bool = True, Q=Q_REG, R=R_REG,
-                       QT=QT_REG) -> LqrLanesResult:
+def LQR_tracking_lanes(x_opt, u_opt, x0, plant=None, *, trajectories: bool = True, gains: bool = True, Q=Q_REG,
+                       R=R_REG, QT=QT_REG) -> LqrLanesResult:
     """LQR tracking of every lane's OWN trajectory (main.py task_2's result into task_3, per lane): lane b's gains
     come from (x_opt[b], u_opt[b]) and its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are
     simulated in closed loop against them.  ``trajectories=False`` returns only the summaries (a Monte-Carlo run has
-    no use for B P trajectories), ``gains=False`` skips the lane-major copy of K."""
+    no use for B P trajectories), ``gains=False`` skips the lane-major copy of K.
+
+    ``plant`` (None: the model the gains are designed on) simulates a mismatched plant per closed loop:
+    the gains stay on the design model, and only the plant step x_{t+1} = RK4(x_t, u_t) of closed loop (b, p) runs on
+    plant[b][p], with the design model's dt.  It is a set number 1-3, a dict of parameter names (params.PARAM_NAMES)
+    to scalars or arrays broadcastable to (B,P) (names left out: the design model's), or an array (11,), (P,11),
+    (B,11), (B,1,11) or (B,P,11) in PARAM_NAMES order, e.g. ``sample_plants(B, P)``; engine.check_plant has the
+    rules.  Where plant[b][p] is the design model the results of (b, p) are bit for bit the call's without
+    ``plant``; a plant that drives its loop to inf or NaN shows in that loop's summaries and nowhere else."""
+    _check_plant(plant, x_opt, x0)
     eng = _eng()
     x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
     x0, flat = _lane_starts(eng, x0, x_opt)
     ws, K = eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=gains)
-    x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat)
+    x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat, plant)
     return LqrLanesResult(x, u, K, s[0], s[1], s[2])
+
+
+def sample_plants(B: int, P: int, rel: float = 0.05, names=("m1", "m2", "I1", "I2", "f1", "f2"), seed: int = 0,
+                  base=None) -> np.ndarray:
+    """Plant parameters for a robustness Monte Carlo, (B,P,11) in params.PARAM_NAMES order, to pass as ``plant=``:
+    each named parameter of ``base`` (a dict; default: set 1) times 1 + U(-rel, rel), independent per (b, p) and
+    parameter, from numpy.random.default_rng(seed); parameters not named are base's own."""
+    base = PARAM_SETS[1] if base is None else base
+    unknown = [n for n in names if n not in PARAM_NAMES]
+    if unknown:
+        raise ValueError(f"unknown plant parameter {unknown[0]!r}: the names are {', '.join(PARAM_NAMES)}")
+    out = np.empty((int(B), int(P), 11))
+    out[:] = [float(base[k]) for k in PARAM_NAMES]
+    rng = np.random.default_rng(seed)
+    for n in names:
+        out[:, :, PARAM_NAMES.index(n)] *= 1.0 + rng.uniform(-rel, rel, (int(B), int(P)))
+    return out
 
 
 def mpc_gains(x_ref, u_ref, T_pred: int = T_PRED, Q=Q_MPC, R=R_MPC, n_steps: int | None = None):
@@ -287,8 +333,8 @@ class MpcBoxLanesResult(MpcLanesResult):
     qp_iters: torch.Tensor | None
 
 
-def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bool = True, T_pred: int = T_PRED,
-                       Q=Q_MPC, R=R_MPC, tau_max=None, max_qp_iters: int = 32) -> MpcLanesResult:
+def MPC_tracking_lanes(x_opt, u_opt, x0, plant=None, *, trajectories: bool = True, gains: bool = True,
+                       T_pred: int = T_PRED, Q=Q_MPC, R=R_MPC, tau_max=None, max_qp_iters: int = 32) -> MpcLanesResult:
     """Receding-horizon MPC tracking of every lane's OWN trajectory (main.py task_2's result into task_4, per lane;
     solve_mpc_tracking :8-69): lane b's first gains come from the T_pred-stage windows along (x_opt[b], u_opt[b]) and
     its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are simulated in closed loop against them.
@@ -300,21 +346,27 @@ def MPC_tracking_lanes(x_opt, u_opt, x0, *, trajectories: bool = True, gains: bo
     (at most ``max_qp_iters`` sweeps each) in the kernel of csrc/mpc_box_lanes.hpp (gym_mpc_box_lanes_rollout; DESIGN
     4.7).  Returns an MpcBoxLanesResult then; where no bound is ever active its x, u and summaries are the
     unlimited call's bit for bit.  ``tau_max=TorqueLimit(18.0)`` adds the projected-Newton fallback to every QP:
-    qp_iters then counts both phases and unconverged only the QPs that neither phase finished."""
+    qp_iters then counts both phases and unconverged only the QPs that neither phase finished.
+
+    ``plant`` as LQR_tracking_lanes, for every ``tau_max`` form: the windows, the pad, Q_T, the QPs and the torque
+    limit stay on the design model, the plant step of closed loop (b, p) runs on plant[b][p]; summaries, qp_iters
+    and unconverged keep their meaning."""
     tau_max, fb = _torque_limit(tau_max)
     if tau_max is not None:
         _check_box(tau_max, T_pred, max_qp_iters, fb)
+    _check_plant(plant, x_opt, x0)
     eng = _eng()
     x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
     x0, flat = _lane_starts(eng, x0, x_opt)
     QT = _mpc_terminal_weight(eng, Q, R)
     if tau_max is None:
         ws, K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=gains)
-        x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat)
+        x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat, plant)
         return MpcLanesResult(x, u, K, s[0], s[1], s[2], QT.clone())
     K = eng.mpc_lanes_gains(x_opt, u_opt, Q, R, QT, int(T_pred), gains=True)[1] if gains else None
     x, u, s, it, unconv = eng.mpc_box_lanes_rollout(x_opt, u_opt, x0, Q, R, QT, int(T_pred), float(tau_max),
-                                                    int(max_qp_iters), trajectories=trajectories, **_fb_kw(fb))
+                                                    int(max_qp_iters), trajectories=trajectories, **_fb_kw(fb),
+                                                    **_plant_kw(eng, plant, x0))
     s, x, u, it, unconv = _drop_starts_axis(flat, s, x, u, it, unconv)
     return MpcBoxLanesResult(x, u, K, s[0], s[1], s[2], QT.clone(), unconv, it)
 

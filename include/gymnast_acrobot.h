@@ -179,6 +179,12 @@ const char* gym_build_id(void);
 
 /* [host] Reduce a reference parameter set {m1,m2,l1,lc1,l2,lc2,I1,I2,g,f1,f2} (dynamics.py:15-61). */
 int gym_model_from_params(const double params[11], double dt, gym_model* out);
+/* [host] n parameter sets at once (dynamics.py:15-61): params (n,11), out (n); row i is bit for bit what
+ * gym_model_from_params gives for row i.  The table of a mismatched plant (below) is made by it, so it also refuses
+ * what no plant can be.  GYM_EINVAL: a NULL pointer, n < 1, a non-finite entry, or a set whose mass matrix
+ * (dynamics.py:63-67) is not positive definite for every theta2: unless d > 0 and d (a - d) > b^2, the denominator
+ * d (a - d) - b^2 cos^2(theta2) of the accelerations.  out is then partly written.  Additive to ABI 18. */
+int gym_models_from_params(const double* params, int64_t n, double dt, gym_model* out);
 
 /* ---------------- per-point primitives (lane-major x (n,4), u (n,2)) ---------------- */
 /* dynamics.py:197-213 continuous_dynamics -> xdot (n,4) */
@@ -532,6 +538,31 @@ int gym_mpc_box_lanes_rollout_fallback(const gym_model* m, const double* x_opt, 
 int gym_timing_create(gym_timing* t);
 int gym_timing_destroy(gym_timing* t);
 int gym_timing_collect(gym_timing* t);
+
+/* ---------------- Per-lane trackers on a mismatched plant: each closed loop simulates its own plant ----------------
+ * (The reference ships three parameter sets, dynamics.py:15-61; a controller designed on one meets another.)  The
+ * controller stays on the design model m: linearisation, gains, windows, pad, Q_T, the QP and the torque limit.  Only
+ * the plant step x_{t+1} = RK4(x_t, u_t) (dynamics.py:177-195) of closed loop (b, p) runs on plant[b][p], with m's dt.
+ * plant [device]: (B,P) rows of gym_model (64 bytes, e.g. gym_models_from_params' output uploaded), 16-byte aligned;
+ * each row's dt is ignored.  Where plant[b][p] equals m bit for bit, every output of (b, p) is bit for bit that of the
+ * entry point without the suffix; the result of (b, p) depends on lane b's inputs, start p and plant[b][p] only (a
+ * plant that drives its own loop to inf or NaN shows in that loop's summaries and nowhere else).
+ * GYM_EINVAL: plant NULL or not 16-byte aligned, then the checks of the entry point each extends.
+ * Additive to ABI 18: no existing entry point or structure changed. */
+/* gym_lqr_lanes_rollout (simulate_tracking, trajectory_tracking.py:206-216) on a workspace gym_lqr_lanes_gains or
+ * gym_mpc_lanes_gains filled (the LQR and the unlimited-MPC closed loop), plant (dynamics.py:15-61) after m */
+int gym_lqr_lanes_rollout_plant(const gym_model* m, const gym_model* plant, const double* x0, int64_t B, int32_t P,
+                                int32_t N, const void* ws, int64_t ws_bytes, double* x_out, double* u_out,
+                                double* summary_out, void* stream);
+/* gym_mpc_box_lanes_rollout_fallback (solve_mpc_tracking's closed loop, trajectory_tracking.py:43-67, with
+ * test_constraints :87-114), plant (dynamics.py:15-61) after m; fallback_iters >= 0 (GYM_EINVAL otherwise), 0 = the
+ * active set alone: gym_mpc_box_lanes_rollout's outputs */
+int gym_mpc_box_lanes_rollout_plant(const gym_model* m, const gym_model* plant, const double* x_opt,
+                                    const double* u_opt, const double* x0, int64_t B, int32_t P, int32_t N, int32_t L,
+                                    const double Q[16], const double R[4], const double* QT_dev, double tau_max,
+                                    int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes,
+                                    double* x_out, double* u_out, double* summary_out, int32_t* qp_iters_out,
+                                    int32_t* unconverged_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,9 +14,12 @@
 (b) 256 lanes: LQR_tracking_lanes against the only route without it, a Python loop of LQR_tracking_batch per lane
     (wall clock around a synchronised loop: the loop is bound by the host and its single-thread gains kernel).
 
+(c) --plant, alone: gym_lqr_lanes_rollout_plant beside gym_lqr_lanes_rollout (plant_arm), written to
+    profiles/plant_mismatch/lqr_lanes_probe.json.
+
 The box state over the whole probe (tools/box_state.py) goes into the file as ``box``.
 
-    python tools/lqr_lanes_probe.py [--lanes 262144] [--reps 7] [--warmup 2] [--arms all]
+    python tools/lqr_lanes_probe.py [--lanes 262144] [--reps 7] [--warmup 2] [--arms all] [--plant]
                                     [--out profiles/lqr_lanes/probe.json]
 """
 from __future__ import annotations
@@ -58,6 +61,76 @@ def timed(fn, warmup, reps):
     return stats(out)
 
 
+def timed_round(fns, warmup, reps):
+    """Several calls timed in alternation (a, b, c, a, b, c, ...), so that a drift of the box meets all alike."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(reps):
+        for fn, us in zip(fns, out):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            us.append(a.elapsed_time(b) * 1e3)
+    return [stats(us) for us in out]
+
+
+def plant_arm(eng, tt, lib, m, g, total, N, warmup, reps):
+    """--plant: gym_lqr_lanes_rollout_plant beside gym_lqr_lanes_rollout on the same workspace, B, P, N: ``total``
+    closed loops as total lanes x 1 start and as total / 64 lanes x 64 starts, summaries only and with trajectories.
+    The new entry point runs twice: on a table whose every row is the design model (the same closed loops bit for
+    bit: what per-thread coefficients cost) and on sample_plants' +-5 % on masses, inertias and friction, one plant
+    per closed loop."""
+    from gymnast_optimalcontrol_amd import _lib
+    Q, R, QT = (np.ascontiguousarray(a, dtype=np.float64) for a in (tt.Q_REG, tt.R_REG, tt.QT_REG))
+    T = N - 1
+    out = {}
+    for B, P in ((total, 1), (max(total // 64, 1), 64)):
+        idx = torch.arange(B, device=eng.device) % 12
+        x_opt, u_opt = eng.t(g["x"])[idx].contiguous(), eng.t(g["u"])[idx].contiguous()
+        ws = eng.lqr_lanes_workspace(B, N)
+        _lib.check(lib.gym_lqr_lanes_gains(m, x_opt.data_ptr(), u_opt.data_ptr(), B, N, Q.ctypes.data, R.ctypes.data,
+                                           QT.ctypes.data, ws.data_ptr(), ws.numel(), None, eng.stream), "gains")
+        x0 = (x_opt[:, 0][:, None] + eng.t(np.random.default_rng(11).uniform(-0.1, 0.1, (12, P, 4)))[idx]).contiguous()
+        tables = (eng.plant_table(1, 12, P)[idx].contiguous(),
+                  eng.plant_table(tt.sample_plants(12, P, seed=0), 12, P)[idx].contiguous())
+        sm = [torch.empty((3, B, P), dtype=torch.float64, device=eng.device) for _ in range(3)]
+        del x_opt, u_opt
+        for traj in (False, True):
+            xo = uo = None
+            if traj:
+                xo = torch.empty((B, P, N, 4), dtype=torch.float64, device=eng.device)
+                uo = torch.empty((B, P, T, 2), dtype=torch.float64, device=eng.device)
+
+            def old():
+                _lib.check(lib.gym_lqr_lanes_rollout(m, x0.data_ptr(), B, P, N, ws.data_ptr(), ws.numel(), _lib.ptr(xo),
+                                                     _lib.ptr(uo), sm[0].data_ptr(), eng.stream), "rollout")
+
+            def new(i):
+                _lib.check(lib.gym_lqr_lanes_rollout_plant(m, tables[i].data_ptr(), x0.data_ptr(), B, P, N,
+                                                           ws.data_ptr(), ws.numel(), _lib.ptr(xo), _lib.ptr(uo),
+                                                           sm[1 + i].data_ptr(), eng.stream), "rollout_plant")
+            a, b, c = timed_round([old, lambda: new(0), lambda: new(1)], warmup, reps)
+            name = f"B{B}_P{P}" + ("_traj" if traj else "")
+            out[name] = {"existing": a, "plant_same_model": b, "plant_sampled": c,
+                         "ratio_same_model_over_existing": b["median_us"] / a["median_us"],
+                         "ratio_sampled_over_existing": c["median_us"] / a["median_us"],
+                         "same_model_summaries_equal_existing": bool(torch.equal(sm[0], sm[1])),
+                         "finite": [bool(torch.isfinite(t).all().item()) for t in sm]}
+            rs, rp = out[name]["ratio_same_model_over_existing"], out[name]["ratio_sampled_over_existing"]
+            print(f"plant {name}: existing {a['median_us']:.0f} us (spread {a['spread_pct']:.1f}%), same model "
+                  f"{b['median_us']:.0f} us (spread {b['spread_pct']:.1f}%, x{rs:.3f}), sampled {c['median_us']:.0f} us "
+                  f"(spread {c['spread_pct']:.1f}%, x{rp:.3f})", flush=True)
+            del xo, uo
+        del ws, x0, tables, sm
+        torch.cuda.empty_cache()
+    return out
+
+
 def with_rate(t, nbytes):
     t["bytes"] = int(nbytes)
     t["TBps"] = nbytes / (t["median_us"] * 1e-6) / 1e12
@@ -71,9 +144,16 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--arms", default="all", help="comma list of gains,rollout,backward,loop (default all)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lqr_lanes", "probe.json"))
+    ap.add_argument("--plant", action="store_true", help="only the mismatched-plant arm: the new rollout entry point "
+                    "beside the existing one (written to profiles/plant_mismatch/lqr_lanes_probe.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", *(("plant_mismatch", "lqr_lanes_probe.json") if args.plant else
+                                                    ("lqr_lanes", "probe.json")))
     arms = {"gains", "rollout", "backward", "loop"} if args.arms == "all" else set(args.arms.split(","))
+    if args.plant:
+        arms = {"plant"}
     from gymnast_optimalcontrol_amd import _lib, trajectory_tracking as tt
     from gymnast_optimalcontrol_amd.solver import BatchedNewtonSolver
     import ctypes as C
@@ -93,6 +173,21 @@ def main():
     import box_state                      # this GPU's clocks, power and cap over the whole probe (sysfs, read only)
     box = box_state.Sampler(torch.cuda.current_device(), 0.02).start()
     box.mark()
+
+    def finish():
+        # the timed regions are milliseconds each, between allocations and host work: the window shows the state the
+        # box was in (clock levels, the cap), not a steady state at the power cap as bench.py's seconds-long legs do
+        res["box"] = box.window() if box.available else {"unmeasured": "no sysfs channels for this device"}
+        box.stop()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", args.out)
+
+    if "plant" in arms:
+        del x_opt, u_opt
+        res["arms"]["plant"] = plant_arm(eng, tt, lib, C.byref(eng.model), g, B, N, args.warmup, args.reps)
+        return finish()
     ws = eng.lqr_lanes_workspace(B, N)
     res["workspace_GB"] = ws.numel() / 1e9
     m = C.byref(eng.model)
@@ -201,14 +296,7 @@ def main():
         res["arms"]["B256"] = out
         print(f"B = 256: LQR_tracking_lanes {out['lanes']['median_us']:.0f} us, Python loop of LQR_tracking_batch "
               f"{out['python_loop']['median_us']:.0f} us, ratio {out['ratio_loop_over_lanes']:.0f}x", flush=True)
-    # the timed regions are milliseconds each, between allocations and host work: the window shows the state the box
-    # was in (clock levels, the cap), not a steady state at the power cap as bench.py's seconds-long legs do
-    res["box"] = box.window() if box.available else {"unmeasured": "no sysfs channels for this device"}
-    box.stop()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print("wrote", args.out)
+    finish()
 
 
 if __name__ == "__main__":

@@ -17,8 +17,10 @@ warm-up and 7 timed repetitions per arm unless stated; median, min, max and the 
      x 64 starts at tau_max 18, each against the fallback-off kernel in the same process: horizon 50 at cap 32 and
      cap 8 (QPs reach the cap and the off arm pays for them), horizon 75 at cap 32 (none does: what the switch costs
      a workload that never uses it).  Not in the default arms; written to profiles/mpc_box_fallback/.
+  p  --plant, alone: gym_mpc_box_lanes_rollout_plant beside the existing entry points on b's shape at tau_max 18,
+     horizon 75, without and with the fallback; written to profiles/plant_mismatch/.
 
-    python tools/mpc_box_lanes_probe.py [--arms abcd] [--reps 7] [--warmup 2] [--big-lanes 262144]
+    python tools/mpc_box_lanes_probe.py [--arms abcd] [--reps 7] [--warmup 2] [--big-lanes 262144] [--plant]
                                         [--out profiles/mpc_box_lanes/probe.json]
 """
 from __future__ import annotations
@@ -60,9 +62,10 @@ def timed(fn, warmup, reps):
 class Call:
     """One gym_mpc_box_lanes_rollout call on preallocated buffers: x_opt (B,N,4), u_opt (B,N-1,2), x0 (B,P,4)."""
 
-    def __init__(self, eng, tt, x_opt, u_opt, x0, L, tau, cap=32, trajectories=True, fb=0):
+    def __init__(self, eng, tt, x_opt, u_opt, x0, L, tau, cap=32, trajectories=True, fb=0, plant=None):
         from gymnast_optimalcontrol_amd import _lib
         self.eng, self._lib, self.fb = eng, _lib, fb
+        self.plant = plant                # a plant_table (B,P,8): gym_mpc_box_lanes_rollout_plant, fb = 0 included
         self.x_opt, self.u_opt, self.x0 = eng.t(x_opt), eng.t(u_opt), eng.t(x0)
         self.B, self.N, self.P, self.L, self.tau, self.cap = x_opt.shape[0], x_opt.shape[1], x0.shape[1], L, tau, cap
         self.Q, self.R = (np.ascontiguousarray(a, dtype=np.float64) for a in (tt.Q_MPC, tt.R_MPC))
@@ -82,7 +85,10 @@ class Call:
                 self.N, self.L, self.Q.ctypes.data, self.R.ctypes.data, self.QT.data_ptr(), float(self.tau), self.cap)
         tail = (self.ws.data_ptr(), self.ws_bytes, p(self.x), p(self.u), self.sm.data_ptr(), p(self.it),
                 self.un.data_ptr(), e.stream)
-        if self.fb:
+        if self.plant is not None:
+            self._lib.check(e.lib.gym_mpc_box_lanes_rollout_plant(head[0], self.plant.data_ptr(), *head[1:], self.fb,
+                                                                  *tail), "gym_mpc_box_lanes_rollout_plant")
+        elif self.fb:
             self._lib.check(e.lib.gym_mpc_box_lanes_rollout_fallback(*head, self.fb, *tail),
                             "gym_mpc_box_lanes_rollout_fallback")
         else:
@@ -100,6 +106,30 @@ class Call:
         return out
 
 
+def timed_round(fns, warmup, reps):
+    """Several calls timed in alternation (a, b, c, a, b, c, ...), so that a drift of the box meets all alike."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(reps):
+        for fn, us in zip(fns, out):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            us.append(a.elapsed_time(b) * 1e3)
+    res = []
+    for us in out:
+        us = np.array(us)
+        res.append({"median_us": float(np.median(us)), "min_us": float(us.min()), "max_us": float(us.max()),
+                    "spread_pct": float(100.0 * (us.max() - us.min()) / np.median(us)),
+                    "reps_us": [float(v) for v in us]})
+    return res
+
+
 def line(name, t):
     print(f"{name}: median {t['median_us'] / 1e3:.2f} ms (min {t['min_us'] / 1e3:.2f}, max {t['max_us'] / 1e3:.2f}, "
           f"spread {t['spread_pct']:.1f}%)", flush=True)
@@ -112,8 +142,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--big-lanes", type=int, default=262144)
     ap.add_argument("--fallback", type=int, default=128, help="fallback_iters of arm f")
+    ap.add_argument("--plant", action="store_true", help="only the mismatched-plant arm: "
+                    "gym_mpc_box_lanes_rollout_plant beside the existing entry points on arm b's shape (written to "
+                    "profiles/plant_mismatch/mpc_box_lanes_probe.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.plant:
+        args.arms = "p"
+        args.out = args.out or os.path.join(ROOT, "profiles", "plant_mismatch", "mpc_box_lanes_probe.json")
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "mpc_box_fallback" if args.arms == "f" else "mpc_box_lanes",
                                 "probe.json" if args.arms != "f" else "lanes_probe.json")
@@ -180,6 +216,39 @@ def main():
         res["box_arm_f"] = box.window() if box.available else {"unmeasured": "no sysfs channels for this device"}
         box.stop()
         print("box", json.dumps(res["box_arm_f"]), flush=True)
+        torch.cuda.empty_cache()
+
+    if "p" in args.arms:
+        # arm b's shape, 128 lanes x 64 starts of the headline trajectory at tau_max 18, horizon 75, cap 32, without and
+        # with the fallback: the existing entry point, the new one on a table whose every row is the design model (the
+        # same closed loops bit for bit, so the ratio is what per-thread coefficients cost), and the new one on
+        # sample_plants' +-5 % (other closed loops with other QPs: a wavefront runs the sweeps of its slowest start),
+        # alternating in the same process on the same inputs and sizes
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import box_state                  # this GPU's clocks and power over the arm (sysfs, read only)
+        box = box_state.Sampler(torch.cuda.current_device(), 0.02).start()
+        box.mark()
+        x_ref, u_ref = eng.t(xr), eng.t(ur)
+        B, P = 128, 64
+        same, table = eng.plant_table(1, B, P), eng.plant_table(tt.sample_plants(B, P, seed=0), B, P)
+        for key, fb in (("active_set", 0), ("fallback", args.fallback)):
+            mk = lambda plant: Call(eng, tt, x_ref[None].expand(B, N, 4), u_ref[None].expand(B, N - 1, 2),   # noqa: E731
+                                    starts.reshape(B, P, 4), 75, 18.0, fb=fb, plant=plant)
+            calls = {"existing": mk(None), "plant_same_model": mk(same), "plant_sampled": mk(table)}
+            arm = dict(zip(calls, timed_round(list(calls.values()), args.warmup, args.reps)))
+            for name, call in calls.items():
+                arm[name].update(call.facts())
+                arm[name]["ratio_to_existing"] = arm[name]["median_us"] / arm["existing"]["median_us"]
+                line(f"p {key} {name} (x{arm[name]['ratio_to_existing']:.3f}, unconverged "
+                     f"{arm[name]['unconverged_qps']}, iterations <= {arm[name]['max_iterations']})", arm[name])
+            arm["same_model_outputs_equal_existing"] = all(
+                torch.equal(getattr(calls["existing"], f), getattr(calls["plant_same_model"], f))
+                for f in ("x", "u", "it", "sm", "un"))
+            res["arms"][f"p_128x64_{key}"] = arm
+            del calls
+        res["box_arm_p"] = box.window() if box.available else {"unmeasured": "no sysfs channels for this device"}
+        box.stop()
+        print("box", json.dumps(res["box_arm_p"]), flush=True)
         torch.cuda.empty_cache()
 
     if "c" in args.arms:
