@@ -1,4 +1,10 @@
-"""ctypes binding of the C-ABI in include/gymnast_acrobot.h (libgymnast_acrobot.so).
+"""ctypes binding of the C-ABI in include/gymnast_acrobot.h (libgymnast_acrobot.so), read from that header.
+
+The header is the one statement of the ABI: its prototypes, structs, #define GYM_* constants and status codes are
+parsed at import (plain re), and the argument types, struct layouts and constants bound here are what it says.  A new
+entry point is its prototype in the header and its definition in a .hip file; nothing is added here.  What the
+parser does not understand it refuses with an ImportError (tests/test_abi_binding_host.py checks the result against
+the C compiler's reading of the header).
 
 The HIP library is the only compute path of this package.  If it is missing, or no HIP
 device is visible, every compute entry point raises -- there is no CPU fallback.
@@ -7,6 +13,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+import types
 
 import torch  # noqa: F401  -- load torch's HIP runtime first so the library binds to the same one
 
@@ -15,145 +23,102 @@ from . import _build
 # GYM_LIB_PATH selects another build of the same library (measurement / diagnostic variants)
 LIB_PATH = os.environ.get("GYM_LIB_PATH") or _build.LIB_PATH
 
-# exported symbols, in include/gymnast_acrobot.h order (tests check every one is present)
-EXPORTS = (
-    "gym_abi_version", "gym_build_id", "gym_model_from_params", "gym_models_from_params",
-    "gym_continuous_dynamics", "gym_rk4_step", "gym_jacobians", "gym_stage_cost_derivs",
-    "gym_pack_lanes", "gym_unpack_lanes", "gym_unpack_gains",
-    "gym_rollout_open_loop", "gym_closed_loop", "gym_total_cost", "gym_backward_sweep", "gym_linearize",
-    "gym_riccati_general",
-    "gym_newton_init", "gym_newton_init_warm", "gym_newton_iteration", "gym_newton_pipeline_split", "gym_newton_phase", "gym_newton_phase_kind",
-    "gym_newton_run",
-    "gym_newton_tail", "gym_newton_tail_scratch", "gym_newton_cand_scratch", "gym_newton_tail_lds",
-    "gym_newton_finalize", "gym_newton_fill_states", "gym_placement_probe", "gym_newton_sigma",
-    "gym_gamma_sweep", "gym_newton_gamma_sweep",
-    "gym_tv_lqr_gains", "gym_dare_fixed_point", "gym_mpc_gains", "gym_lq_forward", "gym_track_rollout", "gym_track_rollout_ex",
-    "gym_mpc_gains_all", "gym_mpc_box_workspace", "gym_mpc_box_qp", "gym_mpc_box_rollout",
-    "gym_mpc_box_qp_fallback", "gym_mpc_box_rollout_fallback",
-    "gym_lqr_lanes_workspace", "gym_lqr_lanes_gains", "gym_lqr_lanes_rollout",
-    "gym_mpc_lanes_gains",
-    "gym_mpc_box_lanes_workspace", "gym_mpc_box_lanes_rollout", "gym_mpc_box_lanes_rollout_fallback",
-    "gym_timing_create", "gym_timing_destroy", "gym_timing_collect",
-    "gym_lqr_lanes_rollout_plant", "gym_mpc_box_lanes_rollout_plant",
-)
+_P = C.c_void_p
+# The type rule, once: a scalar goes by value; a pointer to one of the header's structs is POINTER(<that struct>);
+# every other pointer, and every array declarator of a parameter (const double Q[16], gym_model out[]), is an address
+# (_P).  _POINTEES are the types the header only points at.  Anything else is refused, never guessed.
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "int": C.c_int}
+_POINTEES = ("void", "uint8_t")
+
+
+def _refuse(what: str, text: str):
+    raise ImportError(f"gymnast_acrobot.h: cannot bind {what}: {' '.join(text.split())!r}")
+
+
+def _int(expr: str, consts: dict, what: str) -> int:
+    """The value of a #define, an enumerator or an array size: digits, ( ), <<, *, +, earlier GYM_* constants and an
+    LL suffix (dropped)."""
+    e = re.sub(r"\bGYM_\w+", lambda m: str(consts.get(m.group(), m.group())), expr)
+    e = re.sub(r"(?<=\d)LL\b", "", e)
+    try:
+        if not re.fullmatch(r"(?:\d+|<<|[()*+\s])+", e):
+            raise SyntaxError
+        return int(eval(e, {"__builtins__": {}}))
+    except (SyntaxError, TypeError):         # not in the whitelist, or not an expression ("1 <<", "2 (3)")
+        _refuse(what, expr)
+
+
+def _decl(text: str, what: str):
+    """``[const] type[*] name[size], name ...`` -> (type, is a pointer, [(name, size text or None), ...])"""
+    m = re.fullmatch(r"\s*(?:const\s+)?(\w+)(\s*\*\s*|\s+)(.+?)\s*", text, flags=re.S)
+    names = [re.fullmatch(r"(\w+)\s*(?:\[([^\]]*)\])?", d.strip()) for d in m.group(3).split(",")] if m else [None]
+    if not all(names) or (len(names) > 1 and "*" in m.group(2)):
+        _refuse(what, text)
+    return m.group(1), "*" in m.group(2), [n.groups() for n in names]
+
+
+def _ctype(base: str, pointer: bool, structs: dict, what: str, text: str):
+    if pointer and base in structs:
+        return C.POINTER(structs[base])
+    if pointer and (base in _SCALARS or base in _POINTEES):
+        return _P
+    if not pointer and base in _SCALARS:
+        return _SCALARS[base]
+    _refuse(what, text)
+
+
+def _parse(text: str):
+    """What an ABI header's text declares: consts and status (name -> int), structs (C name -> ctypes class, fields
+    in the header's order) and protos [(return type, name, [(ctypes type, parameter text), ...])] in its order."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    abi = types.SimpleNamespace(consts={}, status={}, structs={}, protos=[])
+    for name, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(GYM_\w+)(.*)$", text, flags=re.M):
+        abi.consts[name] = _int(expr, abi.consts, f"#define {name}")
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for item in filter(str.strip, body.split(",")):
+            m = re.fullmatch(r"\s*(GYM_\w+)\s*=(.*)", item, flags=re.S)
+            if not m:
+                _refuse("enumerator", item)
+            abi.status[m.group(1)] = _int(m.group(2), abi.consts, "enumerator")
+    for body, name in re.findall(r"\btypedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;", text):
+        fields = []
+        for d in filter(str.strip, body.split(";")):
+            what = f"field of {name}"
+            base, pointer, names = _decl(d, what)
+            t = _ctype(base, pointer, abi.structs, what, d)
+            fields += [(n, t if size is None else t * _int(size, abi.consts, what)) for n, size in names]
+        abi.structs[name] = type(name.title().replace("_", ""), (C.Structure,), {"_fields_": fields})
+    if len(abi.structs) != len(re.findall(r"\btypedef\b", text)):
+        _refuse("every typedef", "only " + " ".join(abi.structs))
+    for ret, name, params in re.findall(r"^\s*(int|const\s+char\s*\*)\s+(gym_\w+)\s*\(([^()]*)\)\s*;", text,
+                                        flags=re.M):
+        args = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            what = f"parameter of {name}"
+            base, pointer, ((_, size),) = _decl(p, what)
+            t = _ctype(base, pointer or size is not None, abi.structs, what, p)
+            args.append((t if size is None else _P, " ".join(p.split())))
+        abi.protos.append(("int" if ret == "int" else "const char*", name, args))
+    for name in re.findall(r"\b(gym_\w+)\s*\(", text):
+        if name not in [n for _, n, _ in abi.protos]:
+            _refuse("declaration of", name)
+    return abi
+
+
+with open(os.path.join(_build.INCLUDE, "gymnast_acrobot.h")) as _f:
+    _ABI = _parse(_f.read())
+
+EXPORTS = tuple(name for _, name, _ in _ABI.protos)       # every entry point, in the header's order
+_SIGS = {name: [t for t, _ in args] for _, name, args in _ABI.protos if name != "gym_build_id"}
+# every GYM_<NAME> constant and status code under <NAME> (ABI_VERSION, MAX_BP, MPC_MAX_STAGES, FLAG_*, TRACK_SINGLE,
+# CKPT_INTERVAL, TIMING_POOL, ...; ACTIVE ... PAD) and every struct as Gym<Name> (GymModel ... GymBatch)
+globals().update({name[4:]: v for name, v in {**_ABI.consts, **_ABI.status}.items()})
+globals().update({cls.__name__: cls for cls in _ABI.structs.values()})
+STATUS_NAMES = {v: name[4:].lower() for name, v in _ABI.status.items()}
+# the kernel kinds of gym_timing, which the header names in a comment only
 KERNEL_KINDS = ("backward", "trial", "candidates", "retry", "stats", "phase_odd", "phase_even", "sigma", "run",
                 "tail")
-
-ABI_VERSION = 18        # GYM_ABI_VERSION of the header this binding mirrors
-MAX_BP = 1 << 26         # GYM_MAX_BP
-MPC_MAX_STAGES = 256     # the MPC gain kernels' LDS stage table: T_pred + 2 <= 256 (kMpcMaxStages)
-FLAG_U0_ZERO = 1         # GYM_FLAG_U0_ZERO
-FLAG_X_CKPT = 2          # GYM_FLAG_X_CKPT
-FLAG_RUN_SINGLE = 4      # GYM_FLAG_RUN_SINGLE
-FLAG_REF_LANE = 8        # GYM_FLAG_REF_LANE
-FLAG_SIGMA_STREAM = 16   # GYM_FLAG_SIGMA_STREAM
-TRACK_SINGLE = 1         # GYM_TRACK_SINGLE
-CKPT_INTERVAL = 4        # GYM_CKPT_INTERVAL
-
-ACTIVE, CONVERGED, LS_FAILED, MAX_ITERS, PAD = 0, 1, 2, 3, 4
-STATUS_NAMES = {ACTIVE: "active", CONVERGED: "converged", LS_FAILED: "ls_failed", MAX_ITERS: "max_iters", PAD: "pad"}
-
-
-class GymModel(C.Structure):
-    _fields_ = [(n, C.c_double) for n in ("a", "b", "d", "g1", "g2", "f1", "f2", "dt")]
-
-
-class GymWeights(C.Structure):
-    _fields_ = [("Q", C.c_double * 4), ("R", C.c_double * 2), ("QT", C.c_double * 4)]
-
-
-class GymArmijo(C.Structure):
-    _fields_ = [("tol", C.c_double), ("beta", C.c_double), ("c", C.c_double), ("gamma0", C.c_double),
-                ("max_ls", C.c_int32), ("record_history", C.c_int32)]
-
-
-_P = C.c_void_p
-
-
-TIMING_POOL = 512        # GYM_TIMING_POOL
-
-
-class GymTiming(C.Structure):
-    _fields_ = [("ev", _P * 20), ("ms", C.c_double * 10), ("launches", C.c_int64 * 10), ("pending", C.c_int32),
-                ("pool_used", C.c_int32), ("pool_ev", _P * (2 * TIMING_POOL)), ("pool_kind", C.c_int32 * TIMING_POOL)]
-
-
-class GymBatch(C.Structure):
-    _fields_ = [("B", C.c_int64), ("Bp", C.c_int64), ("N", C.c_int32), ("hist_len", C.c_int32),
-                ("flags", C.c_int32), ("pad", C.c_int32), ("x", _P * 2), ("u", _P * 2), ("K1", _P), ("cs", _P), ("x_ref", _P), ("u_ref", _P),
-                ("cost", _P), ("dJ", _P), ("smax", _P), ("gamma", _P), ("status", _P), ("n_iter", _P),
-                ("res_buf", _P), ("n_roll", _P), ("retry_list", _P), ("counters", _P), ("cand_ok", _P),
-                ("partials", _P), ("stats", _P), ("hist_cost", _P), ("hist_smax", _P), ("lane_map", _P),
-                ("timing", C.POINTER(GymTiming)), ("cand_scratch", _P), ("cand_slots", C.c_int64)]
-
-
-_I64, _I32, _D = C.c_int64, C.c_int32, C.c_double
-_MP, _WP, _AP, _BP = C.POINTER(GymModel), C.POINTER(GymWeights), C.POINTER(GymArmijo), C.POINTER(GymBatch)
-_SIGS = {
-    "gym_abi_version": [],
-    "gym_model_from_params": [_P, _D, _MP],
-    "gym_models_from_params": [_P, _I64, _D, _P],
-    "gym_continuous_dynamics": [_MP, _P, _P, _P, _I64, _P],
-    "gym_rk4_step": [_MP, _P, _P, _P, _I64, _P],
-    "gym_jacobians": [_MP, _P, _P, _P, _P, _I64, _P],
-    "gym_stage_cost_derivs": [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _I64, _P],
-    "gym_pack_lanes": [_P, _P, _I64, _I64, _I32, _I32, _I32, _P],
-    "gym_unpack_lanes": [_P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _P],
-    "gym_unpack_gains": [_P, _P, _I64, _I64, _I32, _P],
-    "gym_rollout_open_loop": [_MP, _WP, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P],
-    "gym_closed_loop": [_MP, _WP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P],
-    "gym_total_cost": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P],
-    "gym_backward_sweep": [_MP, _WP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P],
-    "gym_linearize": [_MP, _WP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P],
-    "gym_riccati_general": [_P] * 12 + [_I64, _I64, _I32, _P],
-    "gym_newton_init": [_MP, _WP, _P, _BP, _P],
-    "gym_newton_init_warm": [_MP, _WP, _P, _P, _P, _BP, _P],
-    "gym_newton_iteration": [_MP, _WP, _AP, _BP, _I32, _P],
-    "gym_newton_pipeline_split": [_BP, C.POINTER(C.c_int64)],
-    "gym_newton_phase_kind": [_BP, C.POINTER(C.c_int32)],
-    "gym_newton_phase": [_MP, _WP, _AP, _BP, _I32, _I32, _P],
-    "gym_newton_run": [_MP, _WP, _AP, _BP, _I32, _I32, _P],
-    "gym_newton_tail": [_MP, _WP, _AP, _BP, _P, _I32, _P, _I64, _I32, _I32, _P],
-    "gym_newton_tail_scratch": [_I32, _I32, _I32, C.POINTER(C.c_int64)],
-    "gym_newton_cand_scratch": [_I32, _I64, C.POINTER(C.c_int64)],
-    "gym_newton_tail_lds": [_I32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
-    "gym_newton_finalize": [_MP, _WP, _BP, _I32, _P, _P, _P, _P, _P],
-    "gym_newton_fill_states": [_MP, _BP, _I32, _P],
-    "gym_placement_probe": [_BP, _I32, _P],
-    "gym_newton_sigma": [_MP, _WP, _BP, _P, _P],
-    "gym_gamma_sweep": [_MP, _WP, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _I64, _I64, _I32, _P],
-    "gym_newton_gamma_sweep": [_MP, _WP, _AP, _BP, _I32, _P, _I32, _P, _P],
-    "gym_tv_lqr_gains": [_P, _P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _D, _P, _P],
-    "gym_dare_fixed_point": [_P, _P, _P, _P, _I32, _D, _P, _P, _P],
-    "gym_mpc_gains": [_MP, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _D, _P, _P, _P, _P],
-    "gym_lq_forward": [_P, _P, _I32, _P, _P, _I32, _D, _P, _P, _I32, _P, _P, _P],
-    "gym_track_rollout": [_MP, _P, _P, _P, _P, _I64, _I32, _P, _P, _P],
-    "gym_track_rollout_ex": [_MP, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P],
-    "gym_mpc_gains_all": [_MP, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _D, _P, _P, _P, _P],
-    "gym_mpc_box_workspace": [_I64, _I32, _I32, C.POINTER(C.c_int64)],
-    "gym_mpc_box_qp": [_P, _P, _P, _I32, _P, _P, _P, _P, _I64, _I32, _D, _I32, _P, _I64, _P, _P, _P, _P, _P],
-    "gym_mpc_box_rollout": [_MP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _P, _I64, _P, _P, _P,
-                            _P, _P],
-    "gym_mpc_box_qp_fallback": [_P, _P, _P, _I32, _P, _P, _P, _P, _I64, _I32, _D, _I32, _I32, _P, _I64, _P, _P, _P, _P,
-                                _P],
-    "gym_mpc_box_rollout_fallback": [_MP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _I32, _P, _I64,
-                                     _P, _P, _P, _P, _P],
-    "gym_lqr_lanes_workspace": [_I64, _I32, C.POINTER(C.c_int64)],
-    "gym_lqr_lanes_gains": [_MP, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _P, _P],
-    "gym_lqr_lanes_rollout": [_MP, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P, _P],
-    "gym_mpc_lanes_gains": [_MP, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P],
-    "gym_mpc_box_lanes_workspace": [_I64, _I32, _I32, C.POINTER(C.c_int64)],
-    "gym_mpc_box_lanes_rollout": [_MP, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _D, _I32, _P, _I64, _P, _P, _P,
-                                  _P, _P, _P],
-    "gym_mpc_box_lanes_rollout_fallback": [_MP, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _D, _I32, _I32, _P, _I64,
-                                           _P, _P, _P, _P, _P, _P],
-    "gym_lqr_lanes_rollout_plant": [_MP, _P, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _P, _P],
-    "gym_mpc_box_lanes_rollout_plant": [_MP, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _D, _I32, _I32, _P,
-                                        _I64, _P, _P, _P, _P, _P, _P],
-    "gym_timing_create": [C.POINTER(GymTiming)],
-    "gym_timing_destroy": [C.POINTER(GymTiming)],
-    "gym_timing_collect": [C.POINTER(GymTiming)],
-}
+assert len(KERNEL_KINDS) == _ABI.consts["GYM_NK"]
 
 _libs: dict = {}
 

@@ -99,7 +99,7 @@ __device__ __forceinline__ double riccati_map_lane(double P, const MapLane& c, d
     return (c.Qij + APA) + APB * K1j;
 }
 
-constexpr int kMpcMaxStages = 256;   // LDS stage table of one workgroup: its 4 windows' stages (L + 2 <= 256)
+constexpr int kMpcMaxStages = GYM_MPC_MAX_STAGES;   // LDS stage table of one workgroup: its 4 windows' stages (L + 2 <= 256)
 
 // ------------------------------------------------------------------------------------------
 // compute_P_inf (:144-165) with doubling jumps.  The reference iterates the Riccati map F from P_0 = Q and stops at

@@ -45,6 +45,7 @@ extern "C" {
 
 #define GYM_ABI_VERSION 18
 #define GYM_MAX_BP (1LL << 26) /* lane stride limit: stream offsets are 32-bit inside one stage      */
+#define GYM_MPC_MAX_STAGES 256 /* the MPC gain kernels' LDS stage table: T_pred + 2 <= 256 (kMpcMaxStages) */
 
 /* gym_batch.flags */
 #define GYM_FLAG_U0_ZERO 1  /* u_ref[:,0] == 0: the unactuated tau1 channel stays exactly zero (u0 starts
@@ -184,7 +185,7 @@ int gym_model_from_params(const double params[11], double dt, gym_model* out);
  * what no plant can be.  GYM_EINVAL: a NULL pointer, n < 1, a non-finite entry, or a set whose mass matrix
  * (dynamics.py:63-67) is not positive definite for every theta2: unless d > 0 and d (a - d) > b^2, the denominator
  * d (a - d) - b^2 cos^2(theta2) of the accelerations.  out is then partly written.  Additive to ABI 18. */
-int gym_models_from_params(const double* params, int64_t n, double dt, gym_model* out);
+int gym_models_from_params(const double* params, int64_t n, double dt, gym_model out[]);
 
 /* ---------------- per-point primitives (lane-major x (n,4), u (n,2)) ---------------- */
 /* dynamics.py:197-213 continuous_dynamics -> xdot (n,4) */
@@ -551,13 +552,13 @@ int gym_timing_collect(gym_timing* t);
  * Additive to ABI 18: no existing entry point or structure changed. */
 /* gym_lqr_lanes_rollout (simulate_tracking, trajectory_tracking.py:206-216) on a workspace gym_lqr_lanes_gains or
  * gym_mpc_lanes_gains filled (the LQR and the unlimited-MPC closed loop), plant (dynamics.py:15-61) after m */
-int gym_lqr_lanes_rollout_plant(const gym_model* m, const gym_model* plant, const double* x0, int64_t B, int32_t P,
+int gym_lqr_lanes_rollout_plant(const gym_model* m, const gym_model plant[], const double* x0, int64_t B, int32_t P,
                                 int32_t N, const void* ws, int64_t ws_bytes, double* x_out, double* u_out,
                                 double* summary_out, void* stream);
 /* gym_mpc_box_lanes_rollout_fallback (solve_mpc_tracking's closed loop, trajectory_tracking.py:43-67, with
  * test_constraints :87-114), plant (dynamics.py:15-61) after m; fallback_iters >= 0 (GYM_EINVAL otherwise), 0 = the
  * active set alone: gym_mpc_box_lanes_rollout's outputs */
-int gym_mpc_box_lanes_rollout_plant(const gym_model* m, const gym_model* plant, const double* x_opt,
+int gym_mpc_box_lanes_rollout_plant(const gym_model* m, const gym_model plant[], const double* x_opt,
                                     const double* u_opt, const double* x0, int64_t B, int32_t P, int32_t N, int32_t L,
                                     const double Q[16], const double R[4], const double* QT_dev, double tau_max,
                                     int32_t max_qp_iters, int32_t fallback_iters, void* ws, int64_t ws_bytes,

@@ -3,11 +3,13 @@
 Every engine method and front-end function of the trackers refuses a bad call through these functions, so each
 rejected class is pinned here once, with the message fragment the callers' tests match on."""
 import inspect
+import os
+import re
 
 import numpy as np
 import pytest
 
-from gymnast_optimalcontrol_amd import _lib, engine as en
+from gymnast_optimalcontrol_amd import _build, _lib, engine as en
 
 X, U, X0 = np.zeros((3, 5, 4)), np.zeros((3, 4, 2)), np.zeros((3, 2, 4))
 Q, R = np.diag([120.0, 100.0, 1e-4, 1e-4]), np.diag([1e-6, 10.0])
@@ -87,6 +89,11 @@ def test_symmetric_weight(name):
 @pytest.mark.parametrize("what", ["per-lane MPC tracking", "the torque-limited QP"])
 def test_window(what):
     assert _lib.MPC_MAX_STAGES == 256
+    # one statement: the ABI header defines it and the kernels' LDS table takes its size from that name
+    hdr = open(os.path.join(_build.INCLUDE, "gymnast_acrobot.h")).read()
+    hpp = open(os.path.join(_build.CSRC, "mpc_gains.hpp")).read()
+    assert re.findall(r"^#define GYM_MPC_MAX_STAGES (\d+)\b", hdr, flags=re.M) == ["256"]
+    assert re.findall(r"\bkMpcMaxStages\s*=\s*(\w+)\s*;", hpp) == ["GYM_MPC_MAX_STAGES"]
     assert en.check_window(2, what) == 2 and en.check_window(254, what) == 254
     assert en.check_window(np.int64(75), what) == 75 and type(en.check_window(np.int64(75), what)) is int
     for L in (1, 255, 0, -3, 256, 1 << 20):
