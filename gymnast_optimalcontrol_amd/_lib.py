@@ -6,6 +6,11 @@ entry point is its prototype in the header and its definition in a .hip file; no
 parser does not understand it refuses with an ImportError (tests/test_abi_binding_host.py checks the result against
 the C compiler's reading of the header).
 
+An extension of the ABI has a header of its own that includes the main one (EXTENSION_HEADERS:
+include/gymnast_acrobot_box.h, the torque-limited Newton solve).  It is read by the same parser with the main header's
+structs and constants known, may declare prototypes only, and its entry points are bound beside the others
+(EXTENSION_EXPORTS, load()); EXPORTS, the structs and the constants stay the main header's.
+
 The HIP library is the only compute path of this package.  If it is missing, or no HIP
 device is visible, every compute entry point raises -- there is no CPU fallback.
 """
@@ -67,11 +72,15 @@ def _ctype(base: str, pointer: bool, structs: dict, what: str, text: str):
     _refuse(what, text)
 
 
-def _parse(text: str):
+def _parse(text: str, base=None):
     """What an ABI header's text declares: consts and status (name -> int), structs (C name -> ctypes class, fields
-    in the header's order) and protos [(return type, name, [(ctypes type, parameter text), ...])] in its order."""
+    in the header's order) and protos [(return type, name, [(ctypes type, parameter text), ...])] in its order.
+    ``base``: the parsed header this one extends (its structs and constants are known here)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     abi = types.SimpleNamespace(consts={}, status={}, structs={}, protos=[])
+    known = dict(base.structs) if base else {}
+    if base:
+        abi.consts.update(base.consts)
     for name, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(GYM_\w+)(.*)$", text, flags=re.M):
         abi.consts[name] = _int(expr, abi.consts, f"#define {name}")
     for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
@@ -85,7 +94,7 @@ def _parse(text: str):
         for d in filter(str.strip, body.split(";")):
             what = f"field of {name}"
             base, pointer, names = _decl(d, what)
-            t = _ctype(base, pointer, abi.structs, what, d)
+            t = _ctype(base, pointer, {**known, **abi.structs}, what, d)
             fields += [(n, t if size is None else t * _int(size, abi.consts, what)) for n, size in names]
         abi.structs[name] = type(name.title().replace("_", ""), (C.Structure,), {"_fields_": fields})
     if len(abi.structs) != len(re.findall(r"\btypedef\b", text)):
@@ -96,7 +105,7 @@ def _parse(text: str):
         for p in ([] if params.strip() == "void" else params.split(",")):
             what = f"parameter of {name}"
             base, pointer, ((_, size),) = _decl(p, what)
-            t = _ctype(base, pointer or size is not None, abi.structs, what, p)
+            t = _ctype(base, pointer or size is not None, {**known, **abi.structs}, what, p)
             args.append((t if size is None else _P, " ".join(p.split())))
         abi.protos.append(("int" if ret == "int" else "const char*", name, args))
     for name in re.findall(r"\b(gym_\w+)\s*\(", text):
@@ -110,6 +119,16 @@ with open(os.path.join(_build.INCLUDE, "gymnast_acrobot.h")) as _f:
 
 EXPORTS = tuple(name for _, name, _ in _ABI.protos)       # every entry point, in the header's order
 _SIGS = {name: [t for t, _ in args] for _, name, args in _ABI.protos if name != "gym_build_id"}
+# the extensions' entry points (prototypes only: no struct, constant or status code of their own)
+EXTENSION_HEADERS = ("gymnast_acrobot_box.h",)
+_EXT_SIGS: dict = {}
+for _h in EXTENSION_HEADERS:
+    with open(os.path.join(_build.INCLUDE, _h)) as _f:
+        _ext = _parse(_f.read(), base=_ABI)
+    if _ext.structs or _ext.status or _ext.consts != _ABI.consts:
+        _refuse("an extension header that declares more than prototypes", _h)
+    _EXT_SIGS.update({name: [t for t, _ in args] for _, name, args in _ext.protos})
+EXTENSION_EXPORTS = tuple(_EXT_SIGS)
 # every GYM_<NAME> constant and status code under <NAME> (ABI_VERSION, MAX_BP, MPC_MAX_STAGES, FLAG_*, TRACK_SINGLE,
 # CKPT_INTERVAL, TIMING_POOL, ...; ACTIVE ... PAD) and every struct as Gym<Name> (GymModel ... GymBatch)
 globals().update({name[4:]: v for name, v in {**_ABI.consts, **_ABI.status}.items()})
@@ -141,7 +160,7 @@ def load(path: str = LIB_PATH):
         if have != want and not os.environ.get("GYM_ALLOW_FOREIGN_BUILD"):
             raise ImportError(f"{path} was built from other sources (build id {have}, tree {want}): stale binary, "
                               "rebuild it (__graft_entry__.build() or python -m gymnast_optimalcontrol_amd._build)")
-        for name, args in _SIGS.items():
+        for name, args in {**_SIGS, **_EXT_SIGS}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = C.c_int

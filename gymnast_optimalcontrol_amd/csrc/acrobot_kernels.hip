@@ -25,6 +25,7 @@
 //   newton_stages.hpp    per-lane building blocks: stage cost, rollouts, trial controls, the backward sweeps
 //   newton_lockstep.hpp  serial and pipelined-phase kernels, post-trial Armijo search
 //   newton_run.hpp       the persistent kernels k_nt_run / k_nt_run2
+//   newton_box.hpp       the torque-limited persistent solve k_nt_run_box / k_nt_sigma_box
 //   newton_tail.hpp      the straggler tail k_nt_tail
 //   newton_util.hpp      API / point kernels, pack / unpack / gather, init, placement probe
 // This file keeps the batch-wide auxiliary kernels (gamma sweeps, statistics, sigma1 re-run, finalize, fill-states),
@@ -37,6 +38,7 @@
 
 #include "acrobot_device.hpp"
 #include "gymnast_acrobot.h"
+#include "gymnast_acrobot_box.h"
 
 using gym::Dyn;
 
@@ -46,6 +48,7 @@ namespace {
 #include "newton_stages.hpp"
 #include "newton_lockstep.hpp"
 #include "newton_run.hpp"
+#include "newton_box.hpp"
 #include "newton_tail.hpp"
 #include "newton_util.hpp"
 
@@ -793,6 +796,27 @@ int gym_newton_run(const gym_model* m, const gym_weights* w, const gym_armijo* a
     return launch_status();
 }
 
+int gym_newton_run_box(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
+                       const double* tau_max, int32_t k0, int32_t k1, void* s) {
+    if (!tau_max || bad_iter_args(m, w, a, b) || k0 < 0 || k1 < k0 ||
+        (b->flags & (GYM_FLAG_X_CKPT | GYM_FLAG_SIGMA_STREAM)))
+        return GYM_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    if (k1 > k0) {
+        TimedLaunch tl(b->timing, 8, st);
+        BoxArgs ra;
+        lane_args(ra, m, w, a, b, k0);
+        ra.retry_list = b->retry_list; ra.counter = b->counters;
+        ra.B = b->B; ra.Bp = b->Bp; ra.N = b->N; ra.k0 = k0; ra.k1 = k1; ra.ext = 0;
+        ra.tau = tau_max;
+        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_nt_run_box<U0Z(), RL()>; }),
+                           dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, ra);
+    }
+    // the statistics after iteration k1 - 1, as gym_newton_run
+    launch_stats(b, Range{0, b->B}, (int)k1 - 1, b->counters, b->stats, nullptr, nullptr, st);
+    return launch_status();
+}
+
 int gym_newton_tail_scratch(int32_t N, int32_t n_lanes, int32_t max_ls, int64_t* doubles_out) {
     if (!doubles_out || N < 2 || N - 1 > TL_MAX_T || n_lanes < 0 || max_ls < 1 || max_ls > BLK) return GYM_EINVAL;
     const int64_t v = (int64_t)n_lanes * max_ls;
@@ -909,6 +933,22 @@ int gym_newton_sigma(const gym_model* m, const gym_weights* w, const gym_batch* 
     return launch_unpack_tiled(SrcSigma{kw(*w), b->cs, b->u[0], b->u[1], b->u_ref, b->n_iter,
                                         (b->flags & GYM_FLAG_REF_LANE) ? 2 * (int64_t)(b->N - 1) : 0}, sig_out, b->B, b->Bp,
                                T, 2, st, b->lane_map);
+}
+
+int gym_newton_sigma_box(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
+                         double* sig_out, void* s) {
+    if (!m || !w || bad_batch(b) || !tau_max || !sig_out || (b->flags & GYM_FLAG_X_CKPT)) return GYM_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    for (int parity = 0; parity < 2; ++parity) {   // sigma1 of each lane's last box sweep, one launch per buffer
+        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_nt_sigma_box<U0Z(), RL()>; }),
+                           dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w), (const double2*)b->x[parity],
+                           b->u[parity], b->x_ref, b->u_ref, b->cs, tau_max, b->n_iter, parity, b->B, b->Bp, b->N);
+        const int e = launch_status();
+        if (e) return e;
+    }
+    return launch_unpack_tiled(SrcSigma{kw(*w), b->cs, b->u[0], b->u[1], b->u_ref, b->n_iter,
+                                        (b->flags & GYM_FLAG_REF_LANE) ? 2 * (int64_t)(b->N - 1) : 0}, sig_out, b->B, b->Bp,
+                               b->N - 1, 2, st, b->lane_map);
 }
 
 static int sweep_grid(int64_t Bp, int G) {

@@ -113,13 +113,22 @@ __device__ __forceinline__ double trial_u1_sig(double2 k0, double2 k1, double cg
     return __builtin_fma(dg, s1, cg + kx);
 }
 
-template <bool WRITE, bool U0Z, bool SIG, bool CK = false, int CP = kNT, bool BAND = true, int PD = 1>
+// Torque limit of the box solver (newton_box.hpp): the trial's tau2 control clipped to [-tau, tau].  A NaN control
+// stays NaN (no comparison with it is true; fmin / fmax alone would turn it into a bound); tau = +inf returns v.
+__device__ __forceinline__ double box_clip(double v, double tau) {
+    const double lo = -tau;
+    return v < lo ? lo : (v > tau ? tau : v);
+}
+
+// BOX (newton_box.hpp): u1_new clipped to [-tau, tau] before the cost, the store and the RK4 step.
+template <bool WRITE, bool U0Z, bool SIG, bool CK = false, int CP = kNT, bool BAND = true, int PD = 1,
+          bool BOX = false>
 __device__ __forceinline__ double rollout_cform(const Dyn& m, const KW& w, const double* __restrict__ u,
                                                 const double2* __restrict__ K1, const double* __restrict__ cs,
                                                 const double* __restrict__ xr, const double* __restrict__ ur,
                                                 double2* __restrict__ xn, double* __restrict__ un, double gamma,
                                                 double gamma0, int64_t l, int64_t Bp, int N, double n0, double n1,
-                                                double n2, double n3) {
+                                                double n2, double n3, double tau = 0.0) {
     const int T = N - 1;
     const double G00 = w.G00, iG00 = w.iG00;
     // lane byte offsets: 2-row wave-blocked pairs (K1, x), planes (cs, u)
@@ -152,8 +161,10 @@ __device__ __forceinline__ double rollout_cform(const Dyn& m, const KW& w, const
         prio_band<BAND ? 1 : PRIO_NONE>(t, T);
         const double* urt = ur + 2 * t;
         const double v0 = U0Z ? 0.0 : trial_u0(q.u0, urt[0], gamma, G00, iG00);   // U0Z: +0 exactly
-        const double v1 = SIG ? trial_u1_sig(q.k0, q.k1, q.cg, q.s1, dg, n0, n1, n2, n3)
-                              : trial_u1(q.k0, q.k1, q.cg, n0, n1, n2, n3);
+        const double v1u = SIG ? trial_u1_sig(q.k0, q.k1, q.cg, q.s1, dg, n0, n1, n2, n3)
+                               : trial_u1(q.k0, q.k1, q.cg, n0, n1, n2, n3);
+        double v1 = v1u;
+        if constexpr (BOX) v1 = box_clip(v1u, tau);
         const double f0 = U0Z ? 0.0 : v0 - urt[0], f1 = v1 - urt[1];
         const KArgs ka = kernarg_consts();   // cost weights re-read per stage (no SGPR spills)
         J = stage_cost<U0Z>(J, ka.w.Q, ka.w.R, n0, n1, n2, n3, xr + 4 * t, f0, f1);
@@ -235,6 +246,16 @@ __device__ __forceinline__ Lin stage_lin(const Dyn& m, const KW& w, const gym::J
     return L;
 }
 
+// One stage of the box solver's sweep (newton_box.hpp; BOX = true below): the caller sets the step's bounds
+// lo = -tau - u1_t, hi = tau - u1_t; step_P decides whether the stage is clamped (the unlimited step
+// s1u = -g1 / G11 leaves [lo, hi]; a NaN s1u does not) and hands step_p the bound it stops at and F = row 1 of
+// B^T P A_d.  A stage that is not clamped is the stage without BOX, bit for bit.
+struct BoxStage {
+    double lo, hi;
+    bool clamped;
+    double s1, F0, F1, F2, F3;
+};
+
 template <bool LAMBDA>
 struct Sweep {
     double P00, P01, P02, P03, P11, P12, P13, P22, P23, P33, p0, p1, p2, p3;
@@ -260,20 +281,21 @@ struct Sweep {
                     k3, s0, s1);
     }
     // the same with the stage's Jacobian already evaluated (it depends on x_t, u_t only, not on P)
-    template <bool U0Z = false>
+    template <bool U0Z = false, bool BOX = false>
     __device__ __forceinline__ void step_j(const Dyn& m, const KW& w, const gym::Jac& J, double2 xa, double2 xb,
                                            double ut0, double ut1, const double* xrt, const double* urt, double& k0,
-                                           double& k1, double& k2, double& k3, double& s0, double& s1) {
-        step_lin<U0Z>(w, stage_lin<U0Z>(m, w, J, xa, xb, ut0, ut1, xrt, urt), k0, k1, k2, k3, s0, s1);
+                                           double& k1, double& k2, double& k3, double& s0, double& s1,
+                                           BoxStage* bx = nullptr) {
+        step_lin<U0Z, BOX>(w, stage_lin<U0Z>(m, w, J, xa, xb, ut0, ut1, xrt, urt), k0, k1, k2, k3, s0, s1, bx);
     }
     // the Riccati update of stage t from its linearisation (stage_lin: a function of x_t, u_t only): the matrix half
     // (gain row 1, P) and then the vector half (sigma, dJ, p, ||sigma||_inf)
-    template <bool U0Z = false>
+    template <bool U0Z = false, bool BOX = false>
     __device__ __forceinline__ void step_lin(const KW& w, const Lin& L, double& k0, double& k1, double& k2,
-                                             double& k3, double& s0, double& s1) {
+                                             double& k3, double& s0, double& s1, BoxStage* bx = nullptr) {
         double G11, iG;
-        step_P(w, L, k0, k1, k2, k3, G11, iG);
-        step_p<U0Z>(w, L, k0, k1, k2, k3, G11, iG, s0, s1);
+        step_P<BOX>(w, L, k0, k1, k2, k3, G11, iG, bx);
+        step_p<U0Z, BOX>(w, L, k0, k1, k2, k3, G11, iG, s0, s1, bx);
     }
     // The matrix half of step_lin: gain row 1 k = -(P b)^T A_d / G11, G11 = 2R1 + b^T P b and its reciprocal, and
     // P <- 2Q + A_d^T P A_d - G11 k k^T.  A function of P and the stage's A_d, b only (not of p), so k_nt_run2
@@ -281,8 +303,10 @@ struct Sweep {
     // FMA contraction within each expression only, never across statements: the bits then do not depend on the
     // context the stage is compiled into (the interleaved sweep of backward_solver_lane_ilp, the sigma1 re-runs,
     // the split sweep of k_nt_run2) -- with cross-statement fusion they did
+    // BOX: a clamped stage (BoxStage) has k = 0, so that G11 k k^T drops out of P: P <- 2Q + A_d^T P A_d
+    template <bool BOX = false>
     __device__ __forceinline__ void step_P(const KW& w, const Lin& L, double& k0, double& k1, double& k2, double& k3,
-                                           double& G11, double& iG) {
+                                           double& G11, double& iG, BoxStage* bx = nullptr) {
 #pragma clang fp contract(on)
         const double dt = L.dt;
         const double A20 = L.A20, A21 = L.A21, A22 = L.A22, A23 = L.A23;
@@ -299,6 +323,15 @@ struct Sweep {
         const double F3 = dt * Pb1 + A23 * Pb2 + A33 * Pb3;
         iG = gym::recip(G11);   // G11 = 2 R1 + b^T P b >= 2 R1 > 0: rcp + two Newton steps
         k0 = -F0 * iG; k1 = -F1 * iG; k2 = -F2 * iG; k3 = -F3 * iG;
+        if constexpr (BOX) {
+            // the unlimited step of this stage: step_p's g1 and sigma1, the same expressions
+            const double g1 = L.r1 + (bd2 * p2 + bd3 * p3);
+            const double s1u = -g1 * iG;
+            bx->clamped = s1u < bx->lo || s1u > bx->hi;
+            bx->s1 = s1u < bx->lo ? bx->lo : bx->hi;
+            bx->F0 = F0; bx->F1 = F1; bx->F2 = F2; bx->F3 = F3;
+            if (bx->clamped) { k0 = 0.0; k1 = 0.0; k2 = 0.0; k3 = 0.0; }
+        }
         // W = P A_d
         const double W00 = P00 + P02 * A20 + P03 * A30, W01 = P01 + P02 * A21 + P03 * A31;
         const double W02 = dt * P00 + P02 * A22 + P03 * A32, W03 = dt * P01 + P02 * A23 + P03 * A33;
@@ -325,9 +358,10 @@ struct Sweep {
     }
     // The vector half of step_lin from the stage's gain row, G11 and 1/G11 (step_P): the costate (LAMBDA), sigma,
     // dJ, p <- q + A_d^T p - K^T G sigma and the running ||sigma||_inf.  Not a function of P.
-    template <bool U0Z = false>
+    // BOX: a clamped stage (BoxStage) takes sigma1 = the bound it stops at and p <- q + A_d^T p + F sigma1
+    template <bool U0Z = false, bool BOX = false>
     __device__ __forceinline__ void step_p(const KW& w, const Lin& L, double k0, double k1, double k2, double k3,
-                                           double G11, double iG, double& s0, double& s1) {
+                                           double G11, double iG, double& s0, double& s1, const BoxStage* bx = nullptr) {
 #pragma clang fp contract(on)
         const double dt = L.dt;
         const double A20 = L.A20, A21 = L.A21, A22 = L.A22, A23 = L.A23;
@@ -343,6 +377,9 @@ struct Sweep {
         }
         const double g1 = r1 + (bd2 * p2 + bd3 * p3);
         s1 = -g1 * iG;
+        if constexpr (BOX) {
+            if (bx->clamped) s1 = bx->s1;
+        }
         if (U0Z) {   // r0 = +0: sigma0 = -0, and r0 sigma0 + g1 sigma1 = g1 sigma1 exactly
             s0 = -0.0;
             const double d1 = g1 * s1;
@@ -352,12 +389,20 @@ struct Sweep {
             dJ += r0 * s0 + g1 * s1;
         }
         // p <- q + A_d^T p - K^T G sigma
+        const double pp0 = p0, pp1 = p1, pp2 = p2, pp3 = p3;   // BOX: p_{t+1} for the clamped form
         const double gs = G11 * s1;
         const double np0 = q0 + (p0 + A20 * p2 + A30 * p3) - k0 * gs;
         const double np1 = q1 + (p1 + A21 * p2 + A31 * p3) - k1 * gs;
         const double np2 = q2 + (dt * p0 + A22 * p2 + A32 * p3) - k2 * gs;
         const double np3 = q3 + (dt * p1 + A23 * p2 + A33 * p3) - k3 * gs;
         p0 = np0; p1 = np1; p2 = np2; p3 = np3;
+        if constexpr (BOX) {
+            const double c0 = q0 + (pp0 + A20 * pp2 + A30 * pp3) + bx->F0 * s1;
+            const double c1 = q1 + (pp1 + A21 * pp2 + A31 * pp3) + bx->F1 * s1;
+            const double c2 = q2 + (dt * pp0 + A22 * pp2 + A32 * pp3) + bx->F2 * s1;
+            const double c3 = q3 + (dt * pp1 + A23 * pp2 + A33 * pp3) + bx->F3 * s1;
+            if (bx->clamped) { p0 = c0; p1 = c1; p2 = c2; p3 = c3; }
+        }
         // U0Z: |sigma0| = 0 never raises smax (>= 0 or NaN)
         smax = U0Z ? gym::nanmax_abs(smax, s1) : gym::nanmax_abs(gym::nanmax_abs(smax, s0), s1);
     }
@@ -528,13 +573,14 @@ __device__ __forceinline__ void backward_solver_lane(const Dyn& m, const KW& w,
 // registers one stage early: prefetch distance 2, three stream sets and two Jacobians in rotation (unrolled by
 // 6, so that no set is copied -- a copy of a loading register waits for its load).  Same per-stage arithmetic
 // as backward_solver_lane (step = jacobian + step_j): the same bits.
-template <bool U0Z, int OUT>
+// BOX (newton_box.hpp): the sweep of the box solver with the lane's torque limit tau, |u1_t| <= tau on every stage.
+template <bool U0Z, int OUT, bool BOX = false>
 __device__ __forceinline__ void backward_solver_lane_ilp(const Dyn& m, const KW& w,
                                                          const double2* __restrict__ x, const double* __restrict__ u,
                                                          const double* __restrict__ xr, const double* __restrict__ ur,
                                                          double2* __restrict__ K1, double* __restrict__ cs, double g0,
                                                          int64_t l, int64_t Bp, int N, double& dJ_out,
-                                                         double& smax_out) {
+                                                         double& smax_out, double tau = 0.0) {
     const int T = N - 1;
     const uint32_t o2 = wbo(l, 2), o1 = (uint32_t)l * 8u;
     const uint32_t row = (uint32_t)Bp * 16u, plane = (uint32_t)Bp * 8u;
@@ -563,7 +609,15 @@ __device__ __forceinline__ void backward_solver_lane_ilp(const Dyn& m, const KW&
         if (t >= 1) Jn = jac(n);
         double k0, k1, k2, k3, s0, s1;
         const KArgs ka = kernarg_consts();
-        S.step_j<U0Z>(ka.m, ka.w, Jc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, k0, k1, k2, k3, s0, s1);
+        if constexpr (BOX) {
+            BoxStage bx;
+            bx.lo = -tau - c.u1;
+            bx.hi = tau - c.u1;
+            S.step_j<U0Z, true>(ka.m, ka.w, Jc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, k0, k1, k2, k3, s0, s1,
+                                &bx);
+        } else {
+            S.step_j<U0Z>(ka.m, ka.w, Jc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, k0, k1, k2, k3, s0, s1);
+        }
         store_stage<OUT>(Kb, Cb, t, row, plane, o2, o1, c.xa, c.xb, c.u1, g0, k0, k1, k2, k3, s1);
     };
     SweepStage A, B, C;

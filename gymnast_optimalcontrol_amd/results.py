@@ -37,6 +37,7 @@ class SolveResult:
     lowocc_lane_iterations: int = 0         # lane-iterations run in the low-occupancy regime (maybe_compact)
     tail_from_iteration: int | None = None  # the outer iteration the straggler tail took over at (None: no tail)
     tail_iterations: int = 0                # outer iterations the tail ran (its slowest lane's, up to the last one)
+    tau_max: torch.Tensor | None = None     # (B,) per-lane torque limits of a limited solve (None: no limit)
 
     def save_npz(self, path, t=None, dt: float = DT):
         """Write the per-lane results as one .npz in the reference's wire format (main.py:74-79, np.savez(x=, u=,

@@ -95,7 +95,7 @@ class BatchedNewtonSolver:
                  capture_lanes=None, capture_every: int = 1, split_waves: bool = True,
                  capture_sigma=(0, 1, 2), tail_lanes: int | None = None, tail_chunk: int = 128,
                  compact: bool | None = None, world_size: int = 1, cand_slots: int | None = None,
-                 arena=False, placement_trials: int | None = None):
+                 arena=False, placement_trials: int | None = None, tau_max=None):
         if B <= 0:
             raise ValueError("batch must hold at least one lane")
         engine.weights.require_gain_solvable()
@@ -107,6 +107,7 @@ class BatchedNewtonSolver:
             raise ValueError("max_ls must be >= 1")
         self._set_u0_flag(u0_zero)
         auto_schedule = pipeline is None and persistent is None
+        pipeline, persistent = self._set_tau_max(tau_max, pipeline, persistent, checkpoint)
         self._choose_schedule(pipeline, persistent, schedule_lanes, checkpoint, chunk, reorder, split_waves)
         self._set_capture(capture_lanes, capture_every, capture_sigma)
         st, placement_trials = self._alloc_streams(arena, placement_trials, auto_schedule)
@@ -154,6 +155,29 @@ class BatchedNewtonSolver:
             raise ValueError("u0_zero=True requires u_ref[:, 0] == 0")
         self.u0_zero = ref_u0_zero if u0_zero is None else bool(u0_zero)
         self._u0_cleared = False   # the flag is off for one warm-started solve whose u_init has tau1 != 0 (init)
+
+    def _set_tau_max(self, tau_max, pipeline, persistent, checkpoint):
+        """The torque limit |tau2| <= tau_max of a limited solve: a number or (B,) per-lane limits, each positive
+        (inf allowed).  Such a solver runs the persistent loop on gym_newton_run_box and nothing else: no pipeline,
+        tail, compaction, low-occupancy switch, checkpointing or candidate scratch.  Returns (pipeline, persistent)
+        as _choose_schedule takes them."""
+        self._tau_in = self.tau_buf = None
+        if tau_max is None:
+            return pipeline, persistent
+        if pipeline or checkpoint or persistent is False:
+            raise ValueError("a torque-limited solve (tau_max) runs the persistent schedule only: no pipeline=True, "
+                             "persistent=False or checkpoint=True")
+        t = self.eng.t(tau_max).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(self.B)
+        if t.numel() != self.B:
+            raise ValueError(f"tau_max must be a number or hold {self.B} lanes, got {t.numel()}")
+        if not bool((t > 0).all().item()):      # zero, negative and NaN limits
+            raise ValueError("tau_max must be positive (inf: no limit)")
+        self._tau_in = t.contiguous().clone()                    # the caller's lane order
+        self.tau_buf = torch.ones(self.Bp, dtype=F64, device=self.eng.device)   # internal order (init); padding: 1
+        self.tau_buf[:self.B] = self._tau_in
+        return False, True
 
     def _choose_schedule(self, pipeline, persistent, schedule_lanes, checkpoint, chunk, reorder, split_waves):
         """serial / pipelined / persistent (``schedule``), and how each runs."""
@@ -507,6 +531,10 @@ class BatchedNewtonSolver:
         if self.ref_lane:   # the references in the lanes' internal order (solve()'s Morton order, or the caller's)
             self.xr_buf[:self.B] = self._xr_in if _ref_perm is None else self._xr_in[_ref_perm]
             self.ur_buf[:self.B] = self._ur_in if _ref_perm is None else self._ur_in[_ref_perm]
+        if self.tau_buf is not None:   # the per-lane limits likewise; a warm start must begin inside its lane's box
+            self.tau_buf[:self.B] = self._tau_in if _ref_perm is None else self._tau_in[_ref_perm]
+            if u_init is not None and bool((u_init[..., 1].abs() > self._tau_in[:, None]).any().item()):
+                raise ValueError("u_init leaves the torque limit: |u_init[:, :, 1]| <= tau_max must hold per lane")
         self._x0 = x0
         if self._pl is not None and self._pl.start(self):
             self._end_placement()
@@ -534,7 +562,10 @@ class BatchedNewtonSolver:
 
     def _run(self, k0: int, k1: int):
         self.launches["run"] += 1
-        self._launch("gym_newton_run", int(k0), int(k1), armijo=True)
+        if self.tau_buf is not None:
+            self._launch("gym_newton_run_box", self.tau_buf.data_ptr(), int(k0), int(k1), armijo=True)
+        else:
+            self._launch("gym_newton_run", int(k0), int(k1), armijo=True)
 
     def tail_run(self, k0: int, k1: int) -> torch.Tensor:
         """Iterations k0 .. k1-1 of every lane still active, on the straggler-tail kernel (gym_newton_tail: one
@@ -651,7 +682,11 @@ class BatchedNewtonSolver:
     def finalize(self):
         B, N, T, dev = self.B, self.N, self.T, self.eng.device
         x, u, K, s = (torch.empty((B, *sh), dtype=F64, device=dev) for sh in ((N, 4), (T, 2), (T, 2, 4), (T, 2)))
-        self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), s.data_ptr())
+        if self.tau_buf is not None:   # the limited sigma: the box sweep re-run, never the unlimited one
+            self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), None)
+            self._launch("gym_newton_sigma_box", self.tau_buf.data_ptr(), s.data_ptr())
+        else:
+            self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), s.data_ptr())
         return x, u, K, s
 
     def states(self, buf: int) -> torch.Tensor:
@@ -667,6 +702,8 @@ class BatchedNewtonSolver:
         from): J(gamma_g) of the trial rollout along iteration k's direction, (B, G); NaN for finished lanes.
         At the trial step sizes gamma_0 beta^i the values are the Armijo trials' costs bit for bit.  Runs
         iteration k's backward sweep, which that iteration recomputes identically, so the solve is unchanged."""
+        if self.tau_buf is not None:
+            raise ValueError("gamma_sweep() is not available on a torque-limited solver (tau_max)")
         g = self.eng.t(gammas).reshape(-1)
         G = int(g.numel())
         if G < 1:
@@ -689,6 +726,8 @@ class BatchedNewtonSolver:
         sigma() reads each iteration's sigma from the stored plane instead of re-running every lane's sweep.  For
         callers that want every iteration's sigma of a few lanes (the drop-in newton_Algorithm's history).  The same
         bits as any schedule."""
+        if self.tau_buf is not None:
+            raise ValueError("stream_sigma() is not available on a torque-limited solver (tau_max)")
         if self.k != 0:
             raise RuntimeError("stream_sigma() must follow init() directly")
         self.pipeline = False
@@ -705,7 +744,10 @@ class BatchedNewtonSolver:
             s[..., 0] = -0.0
             return s
         s = torch.empty((self.B, self.T, 2), dtype=F64, device=self.eng.device)
-        self._launch("gym_newton_sigma", s.data_ptr())
+        if self.tau_buf is not None:
+            self._launch("gym_newton_sigma_box", self.tau_buf.data_ptr(), s.data_ptr())
+        else:
+            self._launch("gym_newton_sigma", s.data_ptr())
         return s
 
     # --- lane compaction ------------------------------------------------------------------
@@ -797,6 +839,8 @@ class BatchedNewtonSolver:
         if self.ref_lane:
             self.xr_buf[moved] = self.xr_buf[src]
             self.ur_buf[moved] = self.ur_buf[src]
+        if self.tau_buf is not None:
+            self.tau_buf[moved] = self.tau_buf[src]
         order = self.lane_order if self.lane_order is not None else torch.arange(B, device=dev)
         self.lane_order = order[perm[:B]]
         self.compactions += 1
@@ -882,7 +926,8 @@ class BatchedNewtonSolver:
                            lane_iterations=int(n_iter.sum().item()), seconds=secs, stats_log=log,
                            schedule=self.schedule, tail_lane_iterations=int(self.tail_lane_its),
                            tail_from_iteration=self.tail_from, tail_iterations=int(self.tail_iters),
-                           compactions=int(self.compactions), lowocc_lane_iterations=int(lowocc), **res)
+                           compactions=int(self.compactions), lowocc_lane_iterations=int(lowocc),
+                           tau_max=None if self._tau_in is None else self._tau_in.clone(), **res)
 
     def resume(self, ckpt: Checkpoint, max_iters: int, **solve_kw) -> SolveResult:
         """Continue a checkpoint (load_checkpoint) for up to ``max_iters`` further iterations:
@@ -918,12 +963,13 @@ class BatchedNewtonSolver:
 def newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, gamma_0=1.0,
                        max_ls=MAX_LINE_SEARCH_ITERS, engine: AcrobotEngine | None = None, hist_len=0,
                        reduce_stats=None, pipeline: bool | None = None,
-                       persistent: bool | None = None, capture_lanes=None, u_init=None) -> SolveResult:
+                       persistent: bool | None = None, capture_lanes=None, u_init=None, tau_max=None) -> SolveResult:
     """Batched newton_Algorithm: x0 (B,4) -> SolveResult (device tensors).  ``u_init`` (B,T,2): start from these
-    controls instead of u = 0 (BatchedNewtonSolver.init)."""
+    controls instead of u = 0 (BatchedNewtonSolver.init).  ``tau_max`` (a number or (B,)): the torque-limited solve
+    (BatchedNewtonSolver's tau_max)."""
     eng = engine or AcrobotEngine()
     x0 = eng.t(x0).reshape(-1, 4)
     solver = BatchedNewtonSolver(eng, x_ref, u_ref, x0.shape[0], tol=tol, beta=beta, c=c, gamma_0=gamma_0,
                                  max_ls=max_ls, hist_len=hist_len, pipeline=pipeline, persistent=persistent,
-                                 capture_lanes=capture_lanes)
+                                 capture_lanes=capture_lanes, tau_max=tau_max)
     return solver.solve(x0, max_iters, reduce_stats=reduce_stats, u_init=u_init)
