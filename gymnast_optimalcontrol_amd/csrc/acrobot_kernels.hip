@@ -26,6 +26,7 @@
 //   newton_lockstep.hpp  serial and pipelined-phase kernels, post-trial Armijo search
 //   newton_run.hpp       the persistent kernels k_nt_run / k_nt_run2
 //   newton_box.hpp       the torque-limited persistent solve k_nt_run_box / k_nt_sigma_box
+//   rk4_lin.hpp          the RK4-exact linearisation: k_nt_run_rk4 / k_nt_sigma_rk4, k_linearize_rk4
 //   newton_tail.hpp      the straggler tail k_nt_tail
 //   newton_util.hpp      API / point kernels, pack / unpack / gather, init, placement probe
 // This file keeps the batch-wide auxiliary kernels (gamma sweeps, statistics, sigma1 re-run, finalize, fill-states),
@@ -39,6 +40,7 @@
 #include "acrobot_device.hpp"
 #include "gymnast_acrobot.h"
 #include "gymnast_acrobot_box.h"
+#include "gymnast_acrobot_rk4lin.h"
 
 using gym::Dyn;
 
@@ -49,6 +51,7 @@ namespace {
 #include "newton_lockstep.hpp"
 #include "newton_run.hpp"
 #include "newton_box.hpp"
+#include "rk4_lin.hpp"
 #include "newton_tail.hpp"
 #include "newton_util.hpp"
 
@@ -525,6 +528,15 @@ int gym_linearize(const gym_model* m, const gym_weights* w, const double* x, con
     return launch_status();
 }
 
+int gym_linearize_rk4(const gym_model* m, const gym_weights* w, const double* x, const double* u, const double* xr,
+                      const double* ur, double* Ad, double* Bd, double* q, double* r, double* qT, int64_t B, int64_t Bp,
+                      int32_t N, void* s) {
+    if (!m || !w || !x || !u || !xr || !ur || !Ad || !Bd || !q || !r || !qT || bad_dims(B, Bp, N)) return GYM_EINVAL;
+    hipLaunchKernelGGL(k_linearize_rk4, dim3(grid_for(B, BLK)), dim3(BLK), 0, (hipStream_t)s, Dyn(*m), kw(*w),
+                       (const double2*)x, u, xr, ur, Ad, Bd, q, r, qT, B, Bp, N);
+    return launch_status();
+}
+
 int gym_riccati_general(const double* A, const double* Bm, const double* Q, const double* R, const double* S,
                         const double* q, const double* r, const double* QT, const double* qT, double* K, double* sigma,
                         double* dJ, int64_t B, int64_t Bp, int32_t T, void* s) {
@@ -796,8 +808,11 @@ int gym_newton_run(const gym_model* m, const gym_weights* w, const gym_armijo* a
     return launch_status();
 }
 
-int gym_newton_run_box(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
-                       const double* tau_max, int32_t k0, int32_t k1, void* s) {
+// gym_newton_run_box / gym_newton_run_rk4: the limited persistent kernel ``kernel_of`` picks (<U0Z, RL>) over the
+// iterations k0 .. k1-1, then the statistics after iteration k1 - 1, as gym_newton_run
+extern "C++" template <class F>
+static int run_limited(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
+                       const double* tau_max, int32_t k0, int32_t k1, void* s, F&& kernel_of) {
     if (!tau_max || bad_iter_args(m, w, a, b) || k0 < 0 || k1 < k0 ||
         (b->flags & (GYM_FLAG_X_CKPT | GYM_FLAG_SIGMA_STREAM)))
         return GYM_EINVAL;
@@ -809,12 +824,20 @@ int gym_newton_run_box(const gym_model* m, const gym_weights* w, const gym_armij
         ra.retry_list = b->retry_list; ra.counter = b->counters;
         ra.B = b->B; ra.Bp = b->Bp; ra.N = b->N; ra.k0 = k0; ra.k1 = k1; ra.ext = 0;
         ra.tau = tau_max;
-        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_nt_run_box<U0Z(), RL()>; }),
-                           dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, ra);
+        hipLaunchKernelGGL(with_variant2(b, kernel_of), dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, ra);
     }
-    // the statistics after iteration k1 - 1, as gym_newton_run
     launch_stats(b, Range{0, b->B}, (int)k1 - 1, b->counters, b->stats, nullptr, nullptr, st);
     return launch_status();
+}
+
+int gym_newton_run_box(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
+                       const double* tau_max, int32_t k0, int32_t k1, void* s) {
+    return run_limited(m, w, a, b, tau_max, k0, k1, s, [](auto U0Z, auto RL) { return k_nt_run_box<U0Z(), RL()>; });
+}
+
+int gym_newton_run_rk4(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
+                       const double* tau_max, int32_t k0, int32_t k1, void* s) {
+    return run_limited(m, w, a, b, tau_max, k0, k1, s, [](auto U0Z, auto RL) { return k_nt_run_rk4<U0Z(), RL()>; });
 }
 
 int gym_newton_tail_scratch(int32_t N, int32_t n_lanes, int32_t max_ls, int64_t* doubles_out) {
@@ -935,20 +958,35 @@ int gym_newton_sigma(const gym_model* m, const gym_weights* w, const gym_batch* 
                                T, 2, st, b->lane_map);
 }
 
-int gym_newton_sigma_box(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
-                         double* sig_out, void* s) {
+// gym_newton_sigma_box / gym_newton_sigma_rk4: sigma1 of each lane's last limited sweep by the re-run kernel
+// ``kernel_of`` picks (<U0Z, RL>), one launch per buffer, then sigma unpacked
+extern "C++" template <class F>
+static int sigma_limited(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
+                         double* sig_out, void* s, F&& kernel_of) {
     if (!m || !w || bad_batch(b) || !tau_max || !sig_out || (b->flags & GYM_FLAG_X_CKPT)) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
-    for (int parity = 0; parity < 2; ++parity) {   // sigma1 of each lane's last box sweep, one launch per buffer
-        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_nt_sigma_box<U0Z(), RL()>; }),
-                           dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w), (const double2*)b->x[parity],
-                           b->u[parity], b->x_ref, b->u_ref, b->cs, tau_max, b->n_iter, parity, b->B, b->Bp, b->N);
+    for (int parity = 0; parity < 2; ++parity) {
+        hipLaunchKernelGGL(with_variant2(b, kernel_of), dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w),
+                           (const double2*)b->x[parity], b->u[parity], b->x_ref, b->u_ref, b->cs, tau_max, b->n_iter,
+                           parity, b->B, b->Bp, b->N);
         const int e = launch_status();
         if (e) return e;
     }
     return launch_unpack_tiled(SrcSigma{kw(*w), b->cs, b->u[0], b->u[1], b->u_ref, b->n_iter,
                                         (b->flags & GYM_FLAG_REF_LANE) ? 2 * (int64_t)(b->N - 1) : 0}, sig_out, b->B, b->Bp,
                                b->N - 1, 2, st, b->lane_map);
+}
+
+int gym_newton_sigma_box(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
+                         double* sig_out, void* s) {
+    return sigma_limited(m, w, b, tau_max, sig_out, s,
+                         [](auto U0Z, auto RL) { return k_nt_sigma_box<U0Z(), RL()>; });
+}
+
+int gym_newton_sigma_rk4(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
+                         double* sig_out, void* s) {
+    return sigma_limited(m, w, b, tau_max, sig_out, s,
+                         [](auto U0Z, auto RL) { return k_nt_sigma_rk4<U0Z(), RL()>; });
 }
 
 static int sweep_grid(int64_t Bp, int G) {

@@ -1,0 +1,421 @@
+// Newton solver kernels: the RK4-exact linearisation and the persistent solve on it, k_nt_run_rk4 / k_nt_sigma_rk4,
+// and the stand-alone primitive k_linearize_rk4.
+// Part of the acrobot_kernels.hip translation unit (included inside its anonymous namespace, in dependency order).
+#pragma once
+
+// ------------------------------------------------------------------------------------------
+// The sweep of newton_Algorithm linearises the dynamics by forward Euler (A_d = I + dt A_c,
+// discretize_linearization :161-164) while every rollout is RK4 (dynamics.py:177-195), so its dJ is not the
+// directional derivative of the cost the Armijo test measures.  Here stage t's matrices are the exact Jacobians of one
+// gym::rk4 step at (x_t, u_t), by the chain rule through the step's own four stage points
+//   X1 = x,  X2 = x + h/2 k1,  X3 = x + h/2 k2,  X4 = x + h k3,   k_i = f(X_i, u) = (omega_i, accel_i).
+// With J_i = df/dx and B_i = df/du at (X_i, u):
+//   d1 = J1,  d2 = J2 (I + h/2 d1),  d3 = J3 (I + h/2 d2),  d4 = J4 (I + h d3),  A_d = I + h/6 (d1 + 2 d2 + 2 d3 + d4)
+//   e1 = B1,  e2 = J2 (h/2 e1) + B2, e3 = J3 (h/2 e2) + B3, e4 = J4 (h e3) + B4, b   = h/6 (e1 + 2 e2 + 2 e3 + e4)
+// J_i has the top rows [0 I] and two dense bottom rows (gym::Jac a2, a3); B_i has only bc2, bc3 in the tau2 column
+// and a zero tau1 column, so column 0 of B_d is exactly zero and is never formed: b is column 1.  Each product
+// J_i M is therefore rows 2, 3 of M on top and two dense rows below.
+// ------------------------------------------------------------------------------------------
+struct Row4 {
+    double c0, c1, c2, c3;
+};
+struct Rk4Lin {
+    Row4 A0, A1, A2, A3;     // A_d, rows
+    double b0, b1, b2, b3;   // column 1 of B_d
+};
+
+// a . M for a dense row a and a matrix with rows M0..M3
+__device__ __forceinline__ Row4 row_mat(const double (&a)[4], const Row4& M0, const Row4& M1, const Row4& M2,
+                                        const Row4& M3) {
+#pragma clang fp contract(on)
+    Row4 r;
+    r.c0 = ((a[0] * M0.c0 + a[1] * M1.c0) + a[2] * M2.c0) + a[3] * M3.c0;
+    r.c1 = ((a[0] * M0.c1 + a[1] * M1.c1) + a[2] * M2.c1) + a[3] * M3.c1;
+    r.c2 = ((a[0] * M0.c2 + a[1] * M1.c2) + a[2] * M2.c2) + a[3] * M3.c2;
+    r.c3 = ((a[0] * M0.c3 + a[1] * M1.c3) + a[2] * M2.c3) + a[3] * M3.c3;
+    return r;
+}
+// row i of I + c d for the row d of a stage derivative (ONE: the column of the identity's 1, -1: none)
+template <int ONE>
+__device__ __forceinline__ Row4 eye_plus(double c, const Row4& d) {
+#pragma clang fp contract(on)
+    Row4 r;
+    r.c0 = (ONE == 0 ? 1.0 : 0.0) + c * d.c0;
+    r.c1 = (ONE == 1 ? 1.0 : 0.0) + c * d.c1;
+    r.c2 = (ONE == 2 ? 1.0 : 0.0) + c * d.c2;
+    r.c3 = (ONE == 3 ? 1.0 : 0.0) + c * d.c3;
+    return r;
+}
+// acc + w d, and h/6-scaled row i of the result
+__device__ __forceinline__ Row4 row_axpy(const Row4& acc, double w, const Row4& d) {
+#pragma clang fp contract(on)
+    Row4 r;
+    r.c0 = acc.c0 + w * d.c0; r.c1 = acc.c1 + w * d.c1; r.c2 = acc.c2 + w * d.c2; r.c3 = acc.c3 + w * d.c3;
+    return r;
+}
+
+// One stage point of the chain rule: from the derivative rows 2, 3 of the previous stage (D2, D3; rows 0, 1 of a
+// stage derivative are rows 2, 3 of the matrix it multiplied, which eye_plus rebuilds) and its input column
+// (e2, e3), the Jacobian J at this stage point gives this stage's rows and column:
+//   M = I + c d_prev,  d = J M: rows 0, 1 = M's rows 2, 3; rows 2, 3 = a2 M, a3 M
+//   v = c e_prev,      e = J v + B: rows 0, 1 = v2, v3;   rows 2, 3 = a2 v + bc2, a3 v + bc3
+struct Rk4Deriv {
+    Row4 d0, d1, d2, d3;
+    double e0, e1, e2, e3;
+};
+__device__ __forceinline__ Rk4Deriv rk4_chain(const gym::Jac& J, double c, const Rk4Deriv& p) {
+#pragma clang fp contract(on)
+    const Row4 M0 = eye_plus<0>(c, p.d0), M1 = eye_plus<1>(c, p.d1);
+    const Row4 M2 = eye_plus<2>(c, p.d2), M3 = eye_plus<3>(c, p.d3);
+    Rk4Deriv n;
+    n.d0 = M2;
+    n.d1 = M3;
+    n.d2 = row_mat(J.a2, M0, M1, M2, M3);
+    n.d3 = row_mat(J.a3, M0, M1, M2, M3);
+    const double v0 = c * p.e0, v1 = c * p.e1, v2 = c * p.e2, v3 = c * p.e3;
+    n.e0 = v2;
+    n.e1 = v3;
+    n.e2 = (((J.a2[0] * v0 + J.a2[1] * v1) + J.a2[2] * v2) + J.a2[3] * v3) + J.bc2;
+    n.e3 = (((J.a3[0] * v0 + J.a3[1] * v1) + J.a3[2] * v2) + J.a3[3] * v3) + J.bc3;
+    return n;
+}
+
+// The exact Jacobians of one gym::rk4 step at x = (x0, x1, x2, x3), u = (., tau2).  The stage points are formed with
+// rk4's sub-step expressions (y = x + h/2 k1, z = x + h/2 k2, v = x + h k3); each point's accelerations come from
+// the sin / cos of its angles reduced from scratch, the values gym::jacobian forms for itself at that point.
+__device__ __forceinline__ Rk4Lin rk4_jacobians(const Dyn& m, double x0, double x1, double x2, double x3, double tau2,
+                                                const gym::PolyRegs& k = gym::poly_lits()) {
+#pragma clang fp contract(on)
+    double s1, c1, s2, c2, a1, b1, a2, b2, a3, b3;
+    // X1 = x
+    gym::fast_sincos(x0, &s1, &c1, k);
+    gym::fast_sincos(x1, &s2, &c2, k);
+    gym::accel_sc(m, s1, c1, s2, c2, x2, x3, tau2, a1, b1);            // k1 = (x2, x3, a1, b1)
+    const gym::Jac J1 = gym::jacobian(m, x0, x1, x2, x3, tau2, k);
+    Rk4Deriv d;
+    d.d0 = Row4{0.0, 0.0, 1.0, 0.0};
+    d.d1 = Row4{0.0, 0.0, 0.0, 1.0};
+    d.d2 = Row4{J1.a2[0], J1.a2[1], J1.a2[2], J1.a2[3]};
+    d.d3 = Row4{J1.a3[0], J1.a3[1], J1.a3[2], J1.a3[3]};
+    d.e0 = 0.0; d.e1 = 0.0; d.e2 = J1.bc2; d.e3 = J1.bc3;
+    Row4 S0 = d.d0, S1 = d.d1, S2 = d.d2, S3 = d.d3;
+    double t0 = d.e0, t1 = d.e1, t2 = d.e2, t3 = d.e3;
+    // X2 = x + h/2 k1
+    const double p0 = x0 + m.h2 * x2, p1 = x1 + m.h2 * x3, y2 = x2 + m.h2 * a1, y3 = x3 + m.h2 * b1;
+    gym::fast_sincos(p0, &s1, &c1, k);
+    gym::fast_sincos(p1, &s2, &c2, k);
+    gym::accel_sc(m, s1, c1, s2, c2, y2, y3, tau2, a2, b2);            // k2 = (y2, y3, a2, b2)
+    d = rk4_chain(gym::jacobian(m, p0, p1, y2, y3, tau2, k), m.h2, d);
+    S0 = row_axpy(S0, 2.0, d.d0); S1 = row_axpy(S1, 2.0, d.d1);
+    S2 = row_axpy(S2, 2.0, d.d2); S3 = row_axpy(S3, 2.0, d.d3);
+    t0 = t0 + 2.0 * d.e0; t1 = t1 + 2.0 * d.e1; t2 = t2 + 2.0 * d.e2; t3 = t3 + 2.0 * d.e3;
+    // X3 = x + h/2 k2
+    const double q0 = x0 + m.h2 * y2, q1 = x1 + m.h2 * y3, z2 = x2 + m.h2 * a2, z3 = x3 + m.h2 * b2;
+    gym::fast_sincos(q0, &s1, &c1, k);
+    gym::fast_sincos(q1, &s2, &c2, k);
+    gym::accel_sc(m, s1, c1, s2, c2, z2, z3, tau2, a3, b3);            // k3 = (z2, z3, a3, b3)
+    d = rk4_chain(gym::jacobian(m, q0, q1, z2, z3, tau2, k), m.h2, d);
+    S0 = row_axpy(S0, 2.0, d.d0); S1 = row_axpy(S1, 2.0, d.d1);
+    S2 = row_axpy(S2, 2.0, d.d2); S3 = row_axpy(S3, 2.0, d.d3);
+    t0 = t0 + 2.0 * d.e0; t1 = t1 + 2.0 * d.e1; t2 = t2 + 2.0 * d.e2; t3 = t3 + 2.0 * d.e3;
+    // X4 = x + h k3
+    const double r0 = x0 + m.h * z2, r1 = x1 + m.h * z3, v2 = x2 + m.h * a3, v3 = x3 + m.h * b3;
+    d = rk4_chain(gym::jacobian(m, r0, r1, v2, v3, tau2, k), m.h, d);
+    S0 = row_axpy(S0, 1.0, d.d0); S1 = row_axpy(S1, 1.0, d.d1);
+    S2 = row_axpy(S2, 1.0, d.d2); S3 = row_axpy(S3, 1.0, d.d3);
+    t0 = t0 + d.e0; t1 = t1 + d.e1; t2 = t2 + d.e2; t3 = t3 + d.e3;
+    // A_d = I + h/6 S,  b = h/6 t
+    const double h6 = m.h * m.h6;
+    Rk4Lin L;
+    L.A0 = eye_plus<0>(h6, S0); L.A1 = eye_plus<1>(h6, S1); L.A2 = eye_plus<2>(h6, S2); L.A3 = eye_plus<3>(h6, S3);
+    L.b0 = h6 * t0; L.b1 = h6 * t1; L.b2 = h6 * t2; L.b3 = h6 * t3;
+    return L;
+}
+
+// ------------------------------------------------------------------------------------------
+// The sweep on dense stage data: Sweep's P (10 values, symmetric) and p recursion with a full 4x4 A_d and a full
+// b, always in the control-limited form of newton_box.hpp (BoxStage; with tau = +inf no stage is ever clamped).
+//   G11 = 2R1 + b^T P b,  F = (P b)^T A_d,  k = -F / G11 (gym::recip),  g1 = r1 + b^T p,  s1u = -g1 / G11
+//   clamped iff s1u < lo or s1u > hi (a NaN is not): k = 0, s1 = the bound, P <- 2Q + A^T P A, p <- q + A^T p + F s1
+//   else: s1 = s1u, P <- 2Q + A^T P A - G11 k k^T, p <- q + A^T p - k G11 s1
+//   dJ += r0 s0 + g1 s1, max|sigma| over s0 and s1.
+// FMA contraction within each expression only, never across statements (as Sweep): the bits do not depend on the
+// kernel the stage is compiled into (k_nt_run_rk4, k_nt_sigma_rk4).
+// ------------------------------------------------------------------------------------------
+struct SweepDense {
+    double P00, P01, P02, P03, P11, P12, P13, P22, P23, P33, p0, p1, p2, p3;
+    double dJ = 0.0, smax = 0.0;
+
+    // terminal conditions from x_N (P = 2 Q_T, p = 2 Q_T dx_N)
+    __device__ __forceinline__ SweepDense(const KW& w, double2 xa, double2 xb, const double* xrT) {
+        P00 = 2.0 * w.QT[0]; P11 = 2.0 * w.QT[1]; P22 = 2.0 * w.QT[2]; P33 = 2.0 * w.QT[3];
+        P01 = P02 = P03 = P12 = P13 = P23 = 0.0;
+        p0 = P00 * (xa.x - xrT[0]); p1 = P11 * (xa.y - xrT[1]);
+        p2 = P22 * (xb.x - xrT[2]); p3 = P33 * (xb.y - xrT[3]);
+    }
+
+    // stage t from its linearisation L at (x_t, u_t): gain row 1 k[0..3], sigma (s0, s1); updates P, p, dJ, smax.
+    // bx: lo, hi set by the caller; clamped, s1 and F filled here.
+    template <bool U0Z>
+    __device__ __forceinline__ void step(const KW& w, const Rk4Lin& L, double2 xa, double2 xb, double ut0, double ut1,
+                                         const double* xrt, const double* urt, BoxStage& bx, double& k0, double& k1,
+                                         double& k2, double& k3, double& s0, double& s1) {
+#pragma clang fp contract(on)
+        const double A00 = L.A0.c0, A01 = L.A0.c1, A02 = L.A0.c2, A03 = L.A0.c3;
+        const double A10 = L.A1.c0, A11 = L.A1.c1, A12 = L.A1.c2, A13 = L.A1.c3;
+        const double A20 = L.A2.c0, A21 = L.A2.c1, A22 = L.A2.c2, A23 = L.A2.c3;
+        const double A30 = L.A3.c0, A31 = L.A3.c1, A32 = L.A3.c2, A33 = L.A3.c3;
+        const double b0 = L.b0, b1 = L.b1, b2 = L.b2, b3 = L.b3;
+        // q_t = 2Q dx_t, r_t = 2R du_t (stage_lin's expressions)
+        const double q0 = w.twoQ[0] * (xa.x - xrt[0]), q1 = w.twoQ[1] * (xa.y - xrt[1]);
+        const double q2 = w.twoQ[2] * (xb.x - xrt[2]), q3 = w.twoQ[3] * (xb.y - xrt[3]);
+        const double r0 = U0Z ? 0.0 : w.G00 * (ut0 - urt[0]);
+        const double r1 = w.twoR1 * (ut1 - urt[1]);
+        // Pb = P b
+        const double Pb0 = ((P00 * b0 + P01 * b1) + P02 * b2) + P03 * b3;
+        const double Pb1 = ((P01 * b0 + P11 * b1) + P12 * b2) + P13 * b3;
+        const double Pb2 = ((P02 * b0 + P12 * b1) + P22 * b2) + P23 * b3;
+        const double Pb3 = ((P03 * b0 + P13 * b1) + P23 * b2) + P33 * b3;
+        const double G11 = w.twoR1 + (((b0 * Pb0 + b1 * Pb1) + b2 * Pb2) + b3 * Pb3);
+        // F = (P b)^T A_d
+        const double F0 = ((Pb0 * A00 + Pb1 * A10) + Pb2 * A20) + Pb3 * A30;
+        const double F1 = ((Pb0 * A01 + Pb1 * A11) + Pb2 * A21) + Pb3 * A31;
+        const double F2 = ((Pb0 * A02 + Pb1 * A12) + Pb2 * A22) + Pb3 * A32;
+        const double F3 = ((Pb0 * A03 + Pb1 * A13) + Pb2 * A23) + Pb3 * A33;
+        const double iG = gym::recip(G11);   // G11 >= 2 R1 > 0: rcp + two Newton steps
+        const double g1 = r1 + (((b0 * p0 + b1 * p1) + b2 * p2) + b3 * p3);
+        const double s1u = -g1 * iG;
+        bx.clamped = s1u < bx.lo || s1u > bx.hi;
+        bx.s1 = s1u < bx.lo ? bx.lo : bx.hi;
+        bx.F0 = F0; bx.F1 = F1; bx.F2 = F2; bx.F3 = F3;
+        k0 = -F0 * iG; k1 = -F1 * iG; k2 = -F2 * iG; k3 = -F3 * iG;
+        s1 = s1u;
+        if (bx.clamped) { k0 = 0.0; k1 = 0.0; k2 = 0.0; k3 = 0.0; s1 = bx.s1; }
+        if (U0Z) {   // r0 = +0: sigma0 = -0, and r0 sigma0 + g1 sigma1 = g1 sigma1 exactly
+            s0 = -0.0;
+            const double d1 = g1 * s1;
+            dJ += d1;
+        } else {
+            s0 = -r0 * w.iG00;
+            dJ += r0 * s0 + g1 * s1;
+        }
+        // p <- q + A_d^T p - k G11 s1 (clamped: + F s1)
+        const double gs = G11 * s1;
+        const double t0 = bx.clamped ? F0 * s1 : -(k0 * gs), t1 = bx.clamped ? F1 * s1 : -(k1 * gs);
+        const double t2 = bx.clamped ? F2 * s1 : -(k2 * gs), t3 = bx.clamped ? F3 * s1 : -(k3 * gs);
+        const double np0 = (q0 + (((A00 * p0 + A10 * p1) + A20 * p2) + A30 * p3)) + t0;
+        const double np1 = (q1 + (((A01 * p0 + A11 * p1) + A21 * p2) + A31 * p3)) + t1;
+        const double np2 = (q2 + (((A02 * p0 + A12 * p1) + A22 * p2) + A32 * p3)) + t2;
+        const double np3 = (q3 + (((A03 * p0 + A13 * p1) + A23 * p2) + A33 * p3)) + t3;
+        p0 = np0; p1 = np1; p2 = np2; p3 = np3;
+        // W = P A_d
+        const double W00 = ((P00 * A00 + P01 * A10) + P02 * A20) + P03 * A30;
+        const double W01 = ((P00 * A01 + P01 * A11) + P02 * A21) + P03 * A31;
+        const double W02 = ((P00 * A02 + P01 * A12) + P02 * A22) + P03 * A32;
+        const double W03 = ((P00 * A03 + P01 * A13) + P02 * A23) + P03 * A33;
+        const double W10 = ((P01 * A00 + P11 * A10) + P12 * A20) + P13 * A30;
+        const double W11 = ((P01 * A01 + P11 * A11) + P12 * A21) + P13 * A31;
+        const double W12 = ((P01 * A02 + P11 * A12) + P12 * A22) + P13 * A32;
+        const double W13 = ((P01 * A03 + P11 * A13) + P12 * A23) + P13 * A33;
+        const double W20 = ((P02 * A00 + P12 * A10) + P22 * A20) + P23 * A30;
+        const double W21 = ((P02 * A01 + P12 * A11) + P22 * A21) + P23 * A31;
+        const double W22 = ((P02 * A02 + P12 * A12) + P22 * A22) + P23 * A32;
+        const double W23 = ((P02 * A03 + P12 * A13) + P22 * A23) + P23 * A33;
+        const double W30 = ((P03 * A00 + P13 * A10) + P23 * A20) + P33 * A30;
+        const double W31 = ((P03 * A01 + P13 * A11) + P23 * A21) + P33 * A31;
+        const double W32 = ((P03 * A02 + P13 * A12) + P23 * A22) + P33 * A32;
+        const double W33 = ((P03 * A03 + P13 * A13) + P23 * A23) + P33 * A33;
+        // P <- 2Q + A_d^T W - G11 k k^T
+        const double gk0 = G11 * k0, gk1 = G11 * k1, gk2 = G11 * k2, gk3 = G11 * k3;
+        const double nP00 = w.twoQ[0] + ((((A00 * W00 + A10 * W10) + A20 * W20) + A30 * W30) - gk0 * k0);
+        const double nP01 = (((A00 * W01 + A10 * W11) + A20 * W21) + A30 * W31) - gk0 * k1;
+        const double nP02 = (((A00 * W02 + A10 * W12) + A20 * W22) + A30 * W32) - gk0 * k2;
+        const double nP03 = (((A00 * W03 + A10 * W13) + A20 * W23) + A30 * W33) - gk0 * k3;
+        const double nP11 = w.twoQ[1] + ((((A01 * W01 + A11 * W11) + A21 * W21) + A31 * W31) - gk1 * k1);
+        const double nP12 = (((A01 * W02 + A11 * W12) + A21 * W22) + A31 * W32) - gk1 * k2;
+        const double nP13 = (((A01 * W03 + A11 * W13) + A21 * W23) + A31 * W33) - gk1 * k3;
+        const double nP22 = w.twoQ[2] + ((((A02 * W02 + A12 * W12) + A22 * W22) + A32 * W32) - gk2 * k2);
+        const double nP23 = (((A02 * W03 + A12 * W13) + A22 * W23) + A32 * W33) - gk2 * k3;
+        const double nP33 = w.twoQ[3] + ((((A03 * W03 + A13 * W13) + A23 * W23) + A33 * W33) - gk3 * k3);
+        P00 = nP00; P01 = nP01; P02 = nP02; P03 = nP03; P11 = nP11; P12 = nP12; P13 = nP13;
+        P22 = nP22; P23 = nP23; P33 = nP33;
+        // U0Z: |sigma0| = 0 never raises smax (>= 0 or NaN)
+        smax = U0Z ? gym::nanmax_abs(smax, s1) : gym::nanmax_abs(gym::nanmax_abs(smax, s0), s1);
+    }
+};
+
+// The solver sweep of one lane on the RK4-exact linearisation, for ONE wavefront per SIMD: as
+// backward_solver_lane_ilp, stage t-1's linearisation (a function of x_{t-1}, u_{t-1} only) is evaluated beside
+// stage t's Riccati update, with three stream sets and two linearisations in rotation (unrolled by 6: no copies).
+template <bool U0Z, int OUT>
+__device__ __forceinline__ void backward_solver_lane_rk4(const double2* __restrict__ x, const double* __restrict__ u,
+                                                         const double* __restrict__ xr, const double* __restrict__ ur,
+                                                         double2* __restrict__ K1, double* __restrict__ cs, double g0,
+                                                         int64_t l, int64_t Bp, int N, double& dJ_out,
+                                                         double& smax_out, double tau) {
+    const int T = N - 1;
+    const uint32_t o2 = wbo(l, 2), o1 = (uint32_t)l * 8u;
+    const uint32_t row = (uint32_t)Bp * 16u, plane = (uint32_t)Bp * 8u;
+    const char* Xb = reinterpret_cast<const char*>(x);
+    const char* Ub = reinterpret_cast<const char*>(u);
+    const char* Kb = reinterpret_cast<const char*>(K1);
+    const char* Cb = reinterpret_cast<const char*>(cs);
+    SweepDense S(kernarg_consts().w, x[wix(T, 0, 2, l, Bp)], x[wix(T, 1, 2, l, Bp)], xr + 4 * T);
+    const gym::PolyRegs pk = gym::poly_vgprs();
+    auto fetch = [&](SweepStage& q, int t) {
+        const auto rX = rsrc(Xb + (int64_t)t * (2 * (int64_t)row)), rU = rsrc(Ub + (int64_t)t * row);
+        q.xa = bld2(rX, o2, 0);
+        q.xb = bld2(rX, o2, WROW);
+        q.u0 = U0Z ? 0.0 : bld1(rU, o1, 0);
+        q.u1 = bld1(rU, o1, plane);
+    };
+    auto lin = [&](const SweepStage& q) {
+        const KArgs ka = kernarg_consts();
+        return rk4_jacobians(ka.m, q.xa.x, q.xa.y, q.xb.x, q.xb.y, q.u1, pk);
+    };
+    // stage t: c = its streams, Lc = its linearisation; n = stage t-1's streams (landed), f <- stage t-2's
+    auto stage = [&](const SweepStage& c, const SweepStage& n, SweepStage& f, const Rk4Lin& Lc, Rk4Lin& Ln, int t) {
+        if (t < 0) return;
+        if (t >= 2) fetch(f, t - 2);
+        if (t >= 1) Ln = lin(n);
+        double k0, k1, k2, k3, s0, s1;
+        const KArgs ka = kernarg_consts();
+        BoxStage bx;
+        bx.lo = -tau - c.u1;
+        bx.hi = tau - c.u1;
+        S.step<U0Z>(ka.w, Lc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, bx, k0, k1, k2, k3, s0, s1);
+        store_stage<OUT>(Kb, Cb, t, row, plane, o2, o1, c.xa, c.xb, c.u1, g0, k0, k1, k2, k3, s1);
+    };
+    SweepStage A, B, C;
+    Rk4Lin L0, L1;
+    fetch(A, T - 1);
+    if (T >= 2) fetch(B, T - 2);
+    L0 = lin(A);
+    for (int t = T - 1; t >= 0; t -= 6) {
+        stage(A, B, C, L0, L1, t);
+        stage(B, C, A, L1, L0, t - 1);
+        stage(C, A, B, L0, L1, t - 2);
+        stage(A, B, C, L1, L0, t - 3);
+        stage(B, C, A, L0, L1, t - 4);
+        stage(C, A, B, L1, L0, t - 5);
+    }
+    dJ_out = S.dJ;
+    smax_out = S.smax;
+}
+
+// k_nt_run_box on the RK4-exact linearisation: the persistent single-wavefront solve whose sweep is
+// backward_solver_lane_rk4 (always OUT_ALL: sigma1 stored, no re-run for lanes that backtrack).  The trials are the
+// box kernel's (clipped control, the same offset form); the Armijo test, gamma <- beta gamma, the update, the stop
+// test, statuses, counters and histories are k_nt_run's.  tau is always present: an unlimited solve passes +inf.
+// The loop is k_nt_run_box's text again rather than one body both kernels instantiate: through a shared body three of
+// k_nt_run_box's four instantiations compile to other machine code (tools/kernel_isa_diff.py).
+template <bool U0Z, bool RL>
+__global__ __launch_bounds__(BLK, 1) void k_nt_run_rk4(BoxArgs args) {
+    const int64_t l = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (l >= args.B) return;
+    int st = kernarg<BoxArgs>()->status[l];
+    for (int k = kernarg<BoxArgs>()->k0; st == GYM_ACTIVE && k < kernarg<BoxArgs>()->k1; ++k) {
+        const int cb = k & 1;
+        {
+            const BoxArgs* R = kernarg<BoxArgs>();
+            double d, s;
+            backward_solver_lane_rk4<U0Z, OUT_ALL>(R->x[cb], R->u[cb], run_xr<RL>(R, l), run_ur<RL>(R, l), R->K1, R->cs,
+                                                   R->a.gamma0, l, R->Bp, R->N, d, s, R->tau[l]);
+            const BoxArgs* Q = kernarg<BoxArgs>();
+            Q->dJ[l] = d;
+            Q->smax[l] = s;
+            if (Q->hist_smax && k < Q->a.hist_len) Q->hist_smax[(int64_t)k * Q->Bp + l] = s;
+        }
+        lane_fence();
+        double Jn;
+        {
+            const BoxArgs* R = kernarg<BoxArgs>();
+            const double2 xa = R->x[cb][wix(0, 0, 2, l, R->Bp)], xb = R->x[cb][wix(0, 1, 2, l, R->Bp)];
+            Jn = rollout_cform<true, U0Z, false, false, kNT, false, 1, true>(
+                R->m, R->w, R->u[cb], R->K1, R->cs, run_xr<RL>(R, l), run_ur<RL>(R, l), R->x[cb ^ 1], R->u[cb ^ 1],
+                R->a.gamma0, R->a.gamma0, l, R->Bp, R->N, xa.x, xa.y, xb.x, xb.y, R->tau[l]);
+        }
+        const BoxArgs* R = kernarg<BoxArgs>();
+        double g = R->a.gamma0;
+        int nr = 1;
+        bool ok = Jn < R->cost[l] + R->a.c * g * R->dJ[l];   // strict Armijo test (:361)
+        for (int j = 1; !ok && j < kernarg<BoxArgs>()->a.max_ls; ++j) {
+            const BoxArgs* P = kernarg<BoxArgs>();
+            g *= P->a.beta;   // gamma_i *= beta, sequentially (:365)
+            const double2 xa = P->x[cb][wix(0, 0, 2, l, P->Bp)], xb = P->x[cb][wix(0, 1, 2, l, P->Bp)];
+            Jn = rollout_cform<true, U0Z, true, false, kNT, false, 1, true>(
+                P->m, P->w, P->u[cb], P->K1, P->cs, run_xr<RL>(P, l), run_ur<RL>(P, l), P->x[cb ^ 1], P->u[cb ^ 1], g,
+                P->a.gamma0, l, P->Bp, P->N, xa.x, xa.y, xb.x, xb.y, P->tau[l]);
+            ++nr;
+            const BoxArgs* Q = kernarg<BoxArgs>();
+            ok = Jn < Q->cost[l] + Q->a.c * g * Q->dJ[l];
+        }
+        const BoxArgs* F = kernarg<BoxArgs>();
+        F->n_roll[l] += nr;
+        F->n_iter[l] += 1;
+        SolverCtl c = F->a;
+        c.k = k;
+        if (ok) {
+            const double s = F->smax[l];
+            accept_lane(c, l, Jn, g, s, F->cost, F->gamma, F->status, F->res_buf, F->hist_cost, F->Bp);
+            if (s < c.tol) st = GYM_CONVERGED;
+        } else {
+            fail_lane(c, l, F->status, F->res_buf);
+            st = GYM_LS_FAILED;
+        }
+        lane_fence();   // the candidate buffer is the next sweep's input
+    }
+}
+
+// sigma1 of each lane's last completed iteration: that iteration's sweep re-run (same inputs, same code: the same
+// bits) into the sigma1 plane.  One launch per buffer parity, as k_nt_sigma_box.
+template <bool U0Z, bool RL>
+__global__ __launch_bounds__(BLK, 1) void k_nt_sigma_rk4(Dyn m, KW w, const double2* __restrict__ x,
+                                                         const double* __restrict__ u, const double* __restrict__ xr,
+                                                         const double* __restrict__ ur, double* __restrict__ cs,
+                                                         const double* __restrict__ tau,
+                                                         const int32_t* __restrict__ n_iter, int parity, int64_t B,
+                                                         int64_t Bp, int N) {
+    const int64_t l = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (l >= B) return;
+    const int it = n_iter[l];
+    if (it <= 0 || ((it - 1) & 1) != parity) return;
+    double d, s;
+    backward_solver_lane_rk4<U0Z, OUT_SIGMA>(x, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
+                                             lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), nullptr, cs, 0.0, l, Bp, N, d, s,
+                                             tau[l]);
+}
+
+// build_stage_lists (:166-181) with the RK4-exact A_d, B_d as plain-double SoA for the generic Riccati path:
+// k_linearize's planes and its q, r, q_T expressions.
+__global__ __launch_bounds__(BLK) void k_linearize_rk4(Dyn m, KW w, const double2* __restrict__ x,
+                                                       const double* __restrict__ u, const double* __restrict__ xr,
+                                                       const double* __restrict__ ur, double* __restrict__ Ad,
+                                                       double* __restrict__ Bd, double* __restrict__ q,
+                                                       double* __restrict__ r, double* __restrict__ qT, int64_t B,
+                                                       int64_t Bp, int N) {
+    const int64_t l = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (l >= B) return;
+    const int T = N - 1;
+    for (int t = 0; t < T; ++t) {
+        const double2 a = x[wix(t, 0, 2, l, Bp)], b = x[wix(t, 1, 2, l, Bp)];
+        const double v0 = u[pix(t, 0, 2, l, Bp)], v1 = u[pix(t, 1, 2, l, Bp)];
+        const Rk4Lin L = rk4_jacobians(m, a.x, a.y, b.x, b.y, v1);
+        const double A[16] = {L.A0.c0, L.A0.c1, L.A0.c2, L.A0.c3, L.A1.c0, L.A1.c1, L.A1.c2, L.A1.c3,
+                              L.A2.c0, L.A2.c1, L.A2.c2, L.A2.c3, L.A3.c0, L.A3.c1, L.A3.c2, L.A3.c3};
+        const double Bv[8] = {0, L.b0, 0, L.b1, 0, L.b2, 0, L.b3};
+#pragma unroll
+        for (int c = 0; c < 16; ++c) Ad[((int64_t)t * 16 + c) * Bp + l] = A[c];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) Bd[((int64_t)t * 8 + c) * Bp + l] = Bv[c];
+        const double xe[4] = {a.x - xr[4 * t], a.y - xr[4 * t + 1], b.x - xr[4 * t + 2], b.y - xr[4 * t + 3]};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) q[((int64_t)t * 4 + c) * Bp + l] = (2.0 * w.Q[c]) * xe[c];
+        r[((int64_t)t * 2) * Bp + l] = (2.0 * w.R[0]) * (v0 - ur[2 * t]);
+        r[((int64_t)t * 2 + 1) * Bp + l] = (2.0 * w.R[1]) * (v1 - ur[2 * t + 1]);
+    }
+    const double2 a = x[wix(T, 0, 2, l, Bp)], b = x[wix(T, 1, 2, l, Bp)];
+    const double xe[4] = {a.x - xr[4 * T], a.y - xr[4 * T + 1], b.x - xr[4 * T + 2], b.y - xr[4 * T + 3]};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) qT[(int64_t)c * Bp + l] = (2.0 * w.QT[c]) * xe[c];
+}

@@ -323,14 +323,18 @@ class AcrobotEngine(PlantTables):
         return (self.unpack_gains(K1, B), self.unpack(sg, B), dJ[:B], sm[:B],
                 self.unpack(lam, B) if want_lambda else None)
 
-    def linearize(self, x, u, x_ref, u_ref):
-        """build_stage_lists: A_d (B,T,4,4), B_d (B,T,4,2), q (B,T,4), r (B,T,2), q_T (B,4)."""
+    def linearize(self, x, u, x_ref, u_ref, method: str = "euler"):
+        """build_stage_lists: A_d (B,T,4,4), B_d (B,T,4,2), q (B,T,4), r (B,T,2), q_T (B,4).  ``method``: "euler", the
+        reference's A_d = I + dt A_c, or "rk4", the exact Jacobians of the RK4 step (gym_linearize_rk4)."""
+        if method not in ("euler", "rk4"):
+            raise ValueError(f'method must be "euler" or "rk4", got {method!r}')
         x_ref, u_ref = self.refs(x_ref, u_ref)
         xs, us, B, Bp, N = self._trajectory(x, u, x_ref, u_ref)
         T = N - 1
         Ad, Bd, q, r = self._buf(T, 16, Bp), self._buf(T, 8, Bp), self._buf(T, 4, Bp), self._buf(T, 2, Bp)
         qT = self._buf(4, Bp)
-        self._call("gym_linearize", self.model, self._w, xs, us, x_ref, u_ref, Ad, Bd, q, r, qT, B, Bp, N)
+        self._call("gym_linearize_rk4" if method == "rk4" else "gym_linearize", self.model, self._w, xs, us, x_ref,
+                   u_ref, Ad, Bd, q, r, qT, B, Bp, N)
         lm = lambda a, *s: a[..., :B].permute(-1, *range(a.ndim - 1)).reshape(B, *s)  # noqa: E731
         return lm(Ad, T, 4, 4), lm(Bd, T, 4, 2), lm(q, T, 4), lm(r, T, 2), lm(qT, 4)
 

@@ -38,13 +38,17 @@ class SolveResult:
     tail_from_iteration: int | None = None  # the outer iteration the straggler tail took over at (None: no tail)
     tail_iterations: int = 0                # outer iterations the tail ran (its slowest lane's, up to the last one)
     tau_max: torch.Tensor | None = None     # (B,) per-lane torque limits of a limited solve (None: no limit)
+    linearization: str = "euler"            # the sweep's linearisation: "euler" (the reference's) or "rk4"
 
     def save_npz(self, path, t=None, dt: float = DT):
         """Write the per-lane results as one .npz in the reference's wire format (main.py:74-79, np.savez(x=, u=,
         t=)): x (B,N,4), u (B,T,2), t (N,) = arange(N) * dt unless given, plus cost, status, n_iter, gamma,
-        n_rollouts, K and sigma, which load_checkpoint / BatchedNewtonSolver.resume continue from.  Host I/O only:
-        tensors on any device."""
+        n_rollouts, K and sigma, which load_checkpoint / BatchedNewtonSolver.resume continue from, and
+        ``linearization`` where it is not the reference's "euler" (a file without it is an Euler solve's).  Host I/O
+        only: tensors on any device."""
         a = {k: getattr(self, k).detach().cpu().numpy() for k in CHECKPOINT_KEYS}
+        if self.linearization != "euler":
+            a["linearization"] = np.array(self.linearization)
         N = a["x"].shape[1]
         a["t"] = np.arange(N) * float(dt) if t is None else np.asarray(t, dtype=np.float64)
         if a["t"].shape != (N,):
@@ -107,6 +111,7 @@ class Checkpoint:
     n_rollouts: torch.Tensor # (B,)   int32
     K: torch.Tensor          # (B,T,2,4)
     sigma: torch.Tensor      # (B,T,2)
+    linearization: str = "euler"   # the sweep the iterates come from; resume() on a solver of the other is refused
 
 
 def load_checkpoint(path, device="cpu") -> Checkpoint:
@@ -140,4 +145,5 @@ def load_checkpoint(path, device="cpu") -> Checkpoint:
             if v.shape != full[k].shape:
                 raise ValueError(f"{path}: '{k}' has shape {v.shape}, expected {full[k].shape}")
             full[k] = v
-    return Checkpoint(**{k: torch.as_tensor(v).to(device) for k, v in full.items()})
+    return Checkpoint(**{k: torch.as_tensor(v).to(device) for k, v in full.items()},
+                      linearization=str(a["linearization"]) if "linearization" in a else "euler")

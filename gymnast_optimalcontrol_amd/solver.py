@@ -95,7 +95,8 @@ class BatchedNewtonSolver:
                  capture_lanes=None, capture_every: int = 1, split_waves: bool = True,
                  capture_sigma=(0, 1, 2), tail_lanes: int | None = None, tail_chunk: int = 128,
                  compact: bool | None = None, world_size: int = 1, cand_slots: int | None = None,
-                 arena=False, placement_trials: int | None = None, tau_max=None):
+                 arena=False, placement_trials: int | None = None, tau_max=None,
+                 linearization: str = "euler"):
         if B <= 0:
             raise ValueError("batch must hold at least one lane")
         engine.weights.require_gain_solvable()
@@ -107,7 +108,7 @@ class BatchedNewtonSolver:
             raise ValueError("max_ls must be >= 1")
         self._set_u0_flag(u0_zero)
         auto_schedule = pipeline is None and persistent is None
-        pipeline, persistent = self._set_tau_max(tau_max, pipeline, persistent, checkpoint)
+        pipeline, persistent = self._set_limited(tau_max, linearization, pipeline, persistent, checkpoint)
         self._choose_schedule(pipeline, persistent, schedule_lanes, checkpoint, chunk, reorder, split_waves)
         self._set_capture(capture_lanes, capture_every, capture_sigma)
         st, placement_trials = self._alloc_streams(arena, placement_trials, auto_schedule)
@@ -156,17 +157,28 @@ class BatchedNewtonSolver:
         self.u0_zero = ref_u0_zero if u0_zero is None else bool(u0_zero)
         self._u0_cleared = False   # the flag is off for one warm-started solve whose u_init has tau1 != 0 (init)
 
-    def _set_tau_max(self, tau_max, pipeline, persistent, checkpoint):
-        """The torque limit |tau2| <= tau_max of a limited solve: a number or (B,) per-lane limits, each positive
-        (inf allowed).  Such a solver runs the persistent loop on gym_newton_run_box and nothing else: no pipeline,
-        tail, compaction, low-occupancy switch, checkpointing or candidate scratch.  Returns (pipeline, persistent)
-        as _choose_schedule takes them."""
+    def _set_limited(self, tau_max, linearization, pipeline, persistent, checkpoint):
+        """The torque limit |tau2| <= tau_max of a limited solve (a number or (B,) per-lane limits, each positive, inf
+        allowed) and the sweep's linearisation: "euler" (the reference's A_d = I + dt A_c) or "rk4" (the exact
+        Jacobians of the RK4 step).  A solver with either runs the persistent loop on its own kernel
+        (gym_newton_run_box / gym_newton_run_rk4) and nothing else: no pipeline, tail, compaction, low-occupancy
+        switch, checkpointing or candidate scratch.  "rk4" without a limit passes +inf limits to that kernel and
+        reports none.  Returns (pipeline, persistent) as _choose_schedule takes them."""
+        if linearization not in ("euler", "rk4"):
+            raise ValueError(f'linearization must be "euler" or "rk4", got {linearization!r}')
+        self.linearization = linearization
+        self._run_fn, self._sigma_fn = (("gym_newton_run_rk4", "gym_newton_sigma_rk4") if linearization == "rk4" else
+                                        ("gym_newton_run_box", "gym_newton_sigma_box"))
         self._tau_in = self.tau_buf = None
-        if tau_max is None:
+        if tau_max is None and linearization == "euler":
             return pipeline, persistent
+        self._limited = "a torque-limited solve (tau_max)" if tau_max is not None else 'linearization="rk4"'
         if pipeline or checkpoint or persistent is False:
-            raise ValueError("a torque-limited solve (tau_max) runs the persistent schedule only: no pipeline=True, "
+            raise ValueError(f"{self._limited} runs the persistent schedule only: no pipeline=True, "
                              "persistent=False or checkpoint=True")
+        if tau_max is None:
+            self.tau_buf = torch.full((self.Bp,), float("inf"), dtype=F64, device=self.eng.device)
+            return False, True
         t = self.eng.t(tau_max).reshape(-1)
         if t.numel() == 1:
             t = t.expand(self.B)
@@ -531,7 +543,7 @@ class BatchedNewtonSolver:
         if self.ref_lane:   # the references in the lanes' internal order (solve()'s Morton order, or the caller's)
             self.xr_buf[:self.B] = self._xr_in if _ref_perm is None else self._xr_in[_ref_perm]
             self.ur_buf[:self.B] = self._ur_in if _ref_perm is None else self._ur_in[_ref_perm]
-        if self.tau_buf is not None:   # the per-lane limits likewise; a warm start must begin inside its lane's box
+        if self._tau_in is not None:   # the per-lane limits likewise; a warm start must begin inside its lane's box
             self.tau_buf[:self.B] = self._tau_in if _ref_perm is None else self._tau_in[_ref_perm]
             if u_init is not None and bool((u_init[..., 1].abs() > self._tau_in[:, None]).any().item()):
                 raise ValueError("u_init leaves the torque limit: |u_init[:, :, 1]| <= tau_max must hold per lane")
@@ -563,7 +575,7 @@ class BatchedNewtonSolver:
     def _run(self, k0: int, k1: int):
         self.launches["run"] += 1
         if self.tau_buf is not None:
-            self._launch("gym_newton_run_box", self.tau_buf.data_ptr(), int(k0), int(k1), armijo=True)
+            self._launch(self._run_fn, self.tau_buf.data_ptr(), int(k0), int(k1), armijo=True)
         else:
             self._launch("gym_newton_run", int(k0), int(k1), armijo=True)
 
@@ -684,7 +696,7 @@ class BatchedNewtonSolver:
         x, u, K, s = (torch.empty((B, *sh), dtype=F64, device=dev) for sh in ((N, 4), (T, 2), (T, 2, 4), (T, 2)))
         if self.tau_buf is not None:   # the limited sigma: the box sweep re-run, never the unlimited one
             self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), None)
-            self._launch("gym_newton_sigma_box", self.tau_buf.data_ptr(), s.data_ptr())
+            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr())
         else:
             self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), s.data_ptr())
         return x, u, K, s
@@ -703,7 +715,7 @@ class BatchedNewtonSolver:
         At the trial step sizes gamma_0 beta^i the values are the Armijo trials' costs bit for bit.  Runs
         iteration k's backward sweep, which that iteration recomputes identically, so the solve is unchanged."""
         if self.tau_buf is not None:
-            raise ValueError("gamma_sweep() is not available on a torque-limited solver (tau_max)")
+            raise ValueError(f"gamma_sweep() is not available on a solver with {self._limited}")
         g = self.eng.t(gammas).reshape(-1)
         G = int(g.numel())
         if G < 1:
@@ -727,7 +739,7 @@ class BatchedNewtonSolver:
         callers that want every iteration's sigma of a few lanes (the drop-in newton_Algorithm's history).  The same
         bits as any schedule."""
         if self.tau_buf is not None:
-            raise ValueError("stream_sigma() is not available on a torque-limited solver (tau_max)")
+            raise ValueError(f"stream_sigma() is not available on a solver with {self._limited}")
         if self.k != 0:
             raise RuntimeError("stream_sigma() must follow init() directly")
         self.pipeline = False
@@ -745,7 +757,7 @@ class BatchedNewtonSolver:
             return s
         s = torch.empty((self.B, self.T, 2), dtype=F64, device=self.eng.device)
         if self.tau_buf is not None:
-            self._launch("gym_newton_sigma_box", self.tau_buf.data_ptr(), s.data_ptr())
+            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr())
         else:
             self._launch("gym_newton_sigma", s.data_ptr())
         return s
@@ -927,7 +939,8 @@ class BatchedNewtonSolver:
                            schedule=self.schedule, tail_lane_iterations=int(self.tail_lane_its),
                            tail_from_iteration=self.tail_from, tail_iterations=int(self.tail_iters),
                            compactions=int(self.compactions), lowocc_lane_iterations=int(lowocc),
-                           tau_max=None if self._tau_in is None else self._tau_in.clone(), **res)
+                           tau_max=None if self._tau_in is None else self._tau_in.clone(),
+                           linearization=self.linearization, **res)
 
     def resume(self, ckpt: Checkpoint, max_iters: int, **solve_kw) -> SolveResult:
         """Continue a checkpoint (load_checkpoint) for up to ``max_iters`` further iterations:
@@ -942,6 +955,9 @@ class BatchedNewtonSolver:
         here.  ``iterations``, ``lane_iterations``, the histories, the statistics log and the captures count this
         segment only."""
         dev = self.eng.device
+        if ckpt.linearization != self.linearization:   # another sweep: not the same solve continued
+            raise ValueError(f'the checkpoint was solved with linearization="{ckpt.linearization}", this solver has '
+                             f'"{self.linearization}"')
         c = {k: getattr(ckpt, k).to(dev) for k in CHECKPOINT_KEYS}
         if c["x"].ndim != 3 or c["x"].shape[0] != self.B or c["x"].shape[1] != self.N:
             raise ValueError(f"the checkpoint holds x {tuple(c['x'].shape)}, this solver ({self.B},{self.N},4)")
@@ -963,13 +979,15 @@ class BatchedNewtonSolver:
 def newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, gamma_0=1.0,
                        max_ls=MAX_LINE_SEARCH_ITERS, engine: AcrobotEngine | None = None, hist_len=0,
                        reduce_stats=None, pipeline: bool | None = None,
-                       persistent: bool | None = None, capture_lanes=None, u_init=None, tau_max=None) -> SolveResult:
+                       persistent: bool | None = None, capture_lanes=None, u_init=None, tau_max=None,
+                       linearization: str = "euler") -> SolveResult:
     """Batched newton_Algorithm: x0 (B,4) -> SolveResult (device tensors).  ``u_init`` (B,T,2): start from these
     controls instead of u = 0 (BatchedNewtonSolver.init).  ``tau_max`` (a number or (B,)): the torque-limited solve
-    (BatchedNewtonSolver's tau_max)."""
+    (BatchedNewtonSolver's tau_max).  ``linearization``: "euler" (the reference's) or "rk4" (the exact Jacobians of
+    the RK4 step, BatchedNewtonSolver's linearization)."""
     eng = engine or AcrobotEngine()
     x0 = eng.t(x0).reshape(-1, 4)
     solver = BatchedNewtonSolver(eng, x_ref, u_ref, x0.shape[0], tol=tol, beta=beta, c=c, gamma_0=gamma_0,
                                  max_ls=max_ls, hist_len=hist_len, pipeline=pipeline, persistent=persistent,
-                                 capture_lanes=capture_lanes, tau_max=tau_max)
+                                 capture_lanes=capture_lanes, tau_max=tau_max, linearization=linearization)
     return solver.solve(x0, max_iters, reduce_stats=reduce_stats, u_init=u_init)

@@ -1,0 +1,176 @@
+"""Newton solve on the RK4-exact linearisation, CPU side: the NumPy restatement (tests/newton_rk4lin_ref.py) the GPU
+tests compare against, the three entry points' binding and host checks, and the keyword's refusals.  No kernel is
+launched here."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import newton_box_ref as nb
+import newton_rk4lin_ref as nr
+from oracle import acrobot_np as onp
+
+SHORT = dict(tol=1e-4, beta=0.7, c=0.5, max_ls=20)
+
+
+def _points(n=6):
+    """A few random states and controls in the swing-up's range (angles to +-pi, velocities to +-6, tau2 to +-15)."""
+    rng = np.random.default_rng(5)
+    x = np.concatenate([rng.uniform(-np.pi, np.pi, (n, 2)), rng.uniform(-6.0, 6.0, (n, 2))], axis=1)
+    u = np.stack([rng.uniform(-1.0, 1.0, n), rng.uniform(-15.0, 15.0, n)], axis=1)
+    return x, u
+
+
+def test_rk4_lin_is_the_jacobian_of_the_rk4_step():
+    """rk4_lin against central differences of onp.rk4 at h = 1e-6: the differences' own error is h^2 |f'''| / 6 plus
+    rounding eps |f| / h, 1e-10 here, so 1e-8 leaves two orders."""
+    x, u = _points()
+    A, B = nr.rk4_lin(x, u)
+    h = 1e-6
+    An = np.zeros_like(A); Bn = np.zeros_like(B)
+    for j in range(4):
+        e = np.zeros(4); e[j] = h
+        An[:, :, j] = (onp.rk4(x + e, u) - onp.rk4(x - e, u)) / (2 * h)
+    for j in range(2):
+        e = np.zeros(2); e[j] = h
+        Bn[:, :, j] = (onp.rk4(x, u + e) - onp.rk4(x, u - e)) / (2 * h)
+    print("max |A - A_fd| %.2e  max |B - B_fd| %.2e" % (np.abs(A - An).max(), np.abs(B - Bn).max()))
+    assert np.abs(A - An).max() < 1e-8 and np.abs(B - Bn).max() < 1e-8
+    # and it is not the Euler pair: the difference is O(dt^2 |A_c|^2), far above the bar
+    Ae, Be = onp.discretize(*onp.jacobians(x, u))
+    assert np.abs(A - Ae).max() > 1e-4 and np.abs(B - Be).max() > 1e-5
+
+
+def test_column_0_of_B_d_is_exactly_zero(task2_refs):
+    x, u = _points()
+    assert not nr.rk4_lin(x, u)[1][:, :, 0].any()
+    x0, xr, ur = nr.short_setup(task2_refs[0], task2_refs[1])
+    xs = onp.simulate_open_loop(x0, np.zeros((5, 40, 2)))
+    A_d, B_d, q, r, QTb, qT = nr.stage_lists_rk4(xs, np.zeros((5, 40, 2)), xr, ur)
+    assert A_d.shape == (5, 40, 4, 4) and B_d.shape == (5, 40, 4, 2) and not B_d[..., 0].any()
+    e = onp.stage_lists(xs, np.zeros((5, 40, 2)), xr, ur)
+    for a, b in zip((q, r, QTb, qT), e[2:]):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("tau", [np.inf, 2.0])
+def test_solve_on_euler_stage_lists_is_the_box_restatement(task2_refs, tau):
+    x0, xr, ur = nr.short_setup(task2_refs[0], task2_refs[1])
+    a = nb.newton_box_solve(x0, xr, ur, 25, tau, gamma_0=0.5, **SHORT)
+    b = nr.newton_rk4lin_solve(x0, xr, ur, 25, tau, gamma_0=0.5, stage_lists=onp.stage_lists, **SHORT)
+    assert set(a) == set(b)
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+
+
+def test_full_newton_steps_converge_on_the_exact_linearisation(task2_refs):
+    """gamma_0 = 1: on the Euler stage lists the line search fails far from the optimum; on the exact ones every lane
+    converges in a few iterations, with and without a limit."""
+    x0, xr, ur = nr.short_setup(task2_refs[0], task2_refs[1])
+    e = nb.newton_box_solve(x0, xr, ur, 30, np.inf, gamma_0=1.0, **SHORT)
+    assert (e["status"] == nr.LS_FAILED).sum() >= 4
+    for tau in (np.inf, 2.0):
+        r = nr.newton_rk4lin_solve(x0, xr, ur, 30, tau, gamma_0=1.0, **SHORT)
+        print("tau", tau, "iterations", r["n_iter"], "rollouts", r["n_rollouts"], "clamped", r["clamped"].sum(1))
+        assert (r["status"] == nr.CONVERGED).all() and (r["n_iter"] <= 8).all()
+        assert (np.abs(r["u"][:, :, 1]) <= tau).all()
+        assert not r["K"][:, :, 0].any()
+
+
+def test_rk4lin_entry_points_are_bound_and_check_their_arguments():
+    """gym_linearize_rk4 / gym_newton_run_rk4 / gym_newton_sigma_rk4 exist with the header's prototypes and return
+    GYM_EINVAL from their host-side checks (the box entry points' conditions) before anything is launched."""
+    from gymnast_optimalcontrol_amd import _build, _lib
+    lib = _lib.load(_build.build())
+    assert _lib.EXTENSION_HEADERS == ("gymnast_acrobot_box.h", "gymnast_acrobot_rk4lin.h")
+    assert _lib.RK4LIN_EXPORTS == ("gym_linearize_rk4", "gym_newton_run_rk4", "gym_newton_sigma_rk4")
+    assert set(_lib.RK4LIN_EXPORTS) <= set(_lib.ALL_EXPORTS) and not set(_lib.RK4LIN_EXPORTS) & set(_lib.EXPORTS)
+    assert any(p.endswith("gymnast_acrobot_rk4lin.h") for p in _build.DEPS)
+    assert any(p.endswith("rk4_lin.hpp") for p in _build.DEPS)
+    P, S = _lib._P, C.POINTER
+    assert _lib._EXT_SIGS["gym_newton_run_rk4"] == _lib._EXT_SIGS["gym_newton_run_box"]
+    assert _lib._EXT_SIGS["gym_newton_sigma_rk4"] == _lib._EXT_SIGS["gym_newton_sigma_box"]
+    assert _lib._EXT_SIGS["gym_linearize_rk4"] == _lib._SIGS["gym_linearize"] == [
+        S(_lib.GymModel), S(_lib.GymWeights), P, P, P, P, P, P, P, P, P, C.c_int64, C.c_int64, C.c_int32, P]
+    for name in _lib.RK4LIN_EXPORTS:
+        assert getattr(lib, name).argtypes == _lib._EXT_SIGS[name]
+    D = 0x10000
+    m, w, a = _lib.GymModel(dt=0.02), _lib.GymWeights(), _lib.GymArmijo(1e-4, 0.7, 0.5, 0.1, 20, 0)
+
+    def batch(B=64, Bp=64, N=501, flags=0):
+        b = _lib.GymBatch(B=B, Bp=Bp, N=N, flags=flags)
+        for f, t in _lib.GymBatch._fields_:
+            if f in ("x", "u"):
+                getattr(b, f)[0] = getattr(b, f)[1] = D
+            elif t is _lib._P and f not in ("hist_cost", "hist_smax", "lane_map"):
+                setattr(b, f, D)
+        return b
+
+    R = C.byref
+    ok = batch()
+    assert lib.gym_newton_run_rk4(None, None, None, None, None, 0, 1, None) == 1
+    assert lib.gym_newton_sigma_rk4(None, None, None, None, None, None) == 1
+    assert lib.gym_newton_run_rk4(R(m), R(w), R(a), R(ok), None, 0, 1, None) == 1          # tau_max NULL
+    assert lib.gym_newton_sigma_rk4(R(m), R(w), R(ok), None, D, None) == 1
+    assert lib.gym_newton_sigma_rk4(R(m), R(w), R(ok), D, None, None) == 1                  # sigma_out NULL
+    assert lib.gym_newton_run_rk4(None, R(w), R(a), R(ok), D, 0, 1, None) == 1
+    assert lib.gym_newton_run_rk4(R(m), R(w), None, R(ok), D, 0, 1, None) == 1
+    assert lib.gym_newton_run_rk4(R(m), R(w), R(a), R(ok), D, 5, 1, None) == 1             # k1 < k0
+    assert lib.gym_newton_run_rk4(R(m), R(w), R(a), R(ok), D, -1, 1, None) == 1
+    bad_ls = _lib.GymArmijo(1e-4, 0.7, 0.5, 0.1, 0, 0)
+    assert lib.gym_newton_run_rk4(R(m), R(w), R(bad_ls), R(ok), D, 0, 1, None) == 1        # max_ls < 1
+    for b in (batch(B=0), batch(B=65, Bp=64), batch(B=60, Bp=100), batch(N=1), batch(Bp=_lib.MAX_BP + 64),
+              batch(flags=_lib.FLAG_X_CKPT), batch(flags=_lib.FLAG_REF_LANE | _lib.FLAG_X_CKPT)):
+        assert lib.gym_newton_run_rk4(R(m), R(w), R(a), R(b), D, 0, 1, None) == 1, (b.B, b.Bp, b.N, b.flags)
+        assert lib.gym_newton_sigma_rk4(R(m), R(w), R(b), D, D, None) == 1, (b.B, b.Bp, b.N, b.flags)
+    assert lib.gym_newton_run_rk4(R(m), R(w), R(a), R(batch(flags=_lib.FLAG_SIGMA_STREAM)), D, 0, 1, None) == 1
+    # gym_linearize_rk4: gym_linearize's checks
+    lin = lambda *p, B=64, Bp=64, N=41: lib.gym_linearize_rk4(*p, B, Bp, N, None)   # noqa: E731
+    full = [R(m), R(w)] + [D] * 9
+    assert lib.gym_linearize_rk4(*[None] * 11, 64, 64, 41, None) == 1
+    for i in range(11):
+        assert lin(*[None if j == i else v for j, v in enumerate(full)]) == 1, i
+    for dims in (dict(B=0), dict(B=65), dict(Bp=100), dict(N=1), dict(Bp=_lib.MAX_BP + 64)):
+        assert lin(*full, **dims) == 1, dims
+
+
+def test_the_abi_headers_of_earlier_versions_are_unchanged():
+    """The extension is additive: it includes gymnast_acrobot.h and declares prototypes only."""
+    import os
+    from gymnast_optimalcontrol_amd import _build
+    with open(os.path.join(_build.INCLUDE, "gymnast_acrobot_rk4lin.h")) as f:
+        text = f.read()
+    assert '#include "gymnast_acrobot.h"' in text and "typedef" not in text and "#define GYM_" not in text
+
+
+def test_solve_result_and_checkpoint_carry_the_linearisation(tmp_path):
+    """SolveResult.linearization defaults to "euler"; save_npz writes it for an "rk4" result, an Euler result's file
+    is the earlier wire format, and a file without the field loads as "euler"."""
+    import dataclasses
+    import torch
+    from gymnast_optimalcontrol_amd.results import CHECKPOINT_KEYS, Checkpoint, SolveResult, load_checkpoint
+    f = {x.name: x for x in dataclasses.fields(SolveResult)}
+    assert f["linearization"].default == "euler"
+    assert {x.name: x for x in dataclasses.fields(Checkpoint)}["linearization"].default == "euler"
+    z = lambda *s: torch.zeros(*s, dtype=torch.float64)   # noqa: E731
+    i = lambda: torch.zeros(2, dtype=torch.int32)         # noqa: E731
+    kw = dict(x=z(2, 5, 4), u=z(2, 4, 2), K=z(2, 4, 2, 4), sigma=z(2, 4, 2), cost=z(2), n_iter=i(), status=i(),
+              n_rollouts=i(), gamma=z(2), iterations=0, lane_iterations=0, seconds=0.0)
+    SolveResult(**kw).save_npz(tmp_path / "e.npz")
+    SolveResult(**kw, linearization="rk4").save_npz(tmp_path / "r.npz")
+    assert set(np.load(tmp_path / "e.npz").files) == set(CHECKPOINT_KEYS) | {"t"}
+    assert set(np.load(tmp_path / "r.npz").files) == set(CHECKPOINT_KEYS) | {"t", "linearization"}
+    assert load_checkpoint(tmp_path / "e.npz").linearization == "euler"
+    assert load_checkpoint(tmp_path / "r.npz").linearization == "rk4"
+
+
+def test_the_keyword_reaches_every_front_end():
+    """linearization= (default "euler") on the solver and both batch functions, method= on AcrobotEngine.linearize;
+    newton_Algorithm (the single-lane history path) has neither."""
+    import inspect
+    from gymnast_optimalcontrol_amd import solver, trajectory_generation as tg
+    from gymnast_optimalcontrol_amd.engine import AcrobotEngine
+    for fn in (solver.BatchedNewtonSolver.__init__, solver.newton_solve_batch, tg.newton_Algorithm_batch):
+        assert inspect.signature(fn).parameters["linearization"].default == "euler", fn
+    assert inspect.signature(AcrobotEngine.linearize).parameters["method"].default == "euler"
+    assert "linearization" not in inspect.signature(tg.newton_Algorithm).parameters

@@ -23,4 +23,5 @@ for line in out.splitlines():
 for k, v in rows.items():
     if "k_nt_" in k or "k_track" in k:
         print(f"{k:42s} VGPR {v.get('VGPRs', '?'):>4}  spillV {v.get('VGPRs Spill', '?'):>3}  "
-              f"spillS {v.get('SGPRs Spill', '?'):>3}  occ {v.get('Occupancy', '?')}")
+              f"spillS {v.get('SGPRs Spill', '?'):>3}  scratch {v.get('ScratchSize', '?'):>3}  "
+              f"occ {v.get('Occupancy', '?')}")
