@@ -24,7 +24,7 @@ SOURCES = [os.path.join(CSRC, "acrobot_kernels.hip"), os.path.join(CSRC, "tracki
 # header -- taken from the directory, so that a new header cannot be edited without changing the build id
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".h"))) + [
     os.path.join(INCLUDE, "gymnast_acrobot.h"), os.path.join(INCLUDE, "gymnast_acrobot_box.h"),
-    os.path.join(INCLUDE, "gymnast_acrobot_rk4lin.h")]
+    os.path.join(INCLUDE, "gymnast_acrobot_rk4lin.h"), os.path.join(INCLUDE, "gymnast_acrobot_models.h")]
 ARCH = os.environ.get("GYM_OFFLOAD_ARCH", "gfx950")
 BUILD_ID_TAG = b"gym-build-id:"      # marker in front of the id string inside the library's .rodata
 

@@ -23,6 +23,15 @@ struct Dyn {
           f2(m.f2), h(m.dt), h2(m.dt * 0.5), h6(1.0 / 6.0) {}
 };
 
+// Row `row` of a device table of gym_model (64 bytes a row, 16-byte aligned: four 16-byte loads) made a Dyn by the
+// constructor the host uses, so bb and dad are the same single-rounded operations on both sides; h, h2, h6 are m's
+// (the row's dt is ignored).  The nine coefficients are then per-thread registers, not scalars.
+__device__ __forceinline__ Dyn model_row(const Dyn& m, const gym_model* rows, int64_t row) {
+    const double2* r = reinterpret_cast<const double2*>(rows + row);
+    const double2 ab = r[0], dg = r[1], gf = r[2], fd = r[3];
+    return Dyn(gym_model{ab.x, ab.y, dg.x, dg.y, gf.x, gf.y, fd.x, m.h});
+}
+
 // ------------------------------------------------------------------------------------------
 // fp64 sin/cos for the arguments this model produces.  ocml's sincos carries the reduced
 // argument as a double-double and a Payne-Hanek path (~60-75 VALU per call); the angles of an

@@ -26,6 +26,7 @@
 //   newton_lockstep.hpp  serial and pipelined-phase kernels, post-trial Armijo search
 //   newton_run.hpp       the persistent kernels k_nt_run / k_nt_run2
 //   newton_box.hpp       the torque-limited persistent solve k_nt_run_box / k_nt_sigma_box
+//   newton_models.hpp    the persistent solve on per-lane models k_nt_run_models / k_nt_sigma_models
 //   rk4_lin.hpp          the RK4-exact linearisation: k_nt_run_rk4 / k_nt_sigma_rk4, k_linearize_rk4
 //   newton_tail.hpp      the straggler tail k_nt_tail
 //   newton_util.hpp      API / point kernels, pack / unpack / gather, init, placement probe
@@ -41,6 +42,7 @@
 #include "gymnast_acrobot.h"
 #include "gymnast_acrobot_box.h"
 #include "gymnast_acrobot_rk4lin.h"
+#include "gymnast_acrobot_models.h"
 
 using gym::Dyn;
 
@@ -51,6 +53,7 @@ namespace {
 #include "newton_lockstep.hpp"
 #include "newton_run.hpp"
 #include "newton_box.hpp"
+#include "newton_models.hpp"
 #include "rk4_lin.hpp"
 #include "newton_tail.hpp"
 #include "newton_util.hpp"
@@ -568,20 +571,29 @@ static hipError_t reset_batch(const gym_batch* b, bool zero_u0, hipStream_t st) 
     return e;
 }
 
-int gym_newton_init(const gym_model* m, const gym_weights* w, const double* x0, const gym_batch* b, void* s) {
+// gym_newton_init / gym_newton_init_warm; models: the (Bp) table of gym_newton_init_models, or null for m on every lane
+static int init_cold(const gym_model* m, const gym_model* models, const gym_weights* w, const double* x0,
+                     const gym_batch* b, void* s) {
     if (!m || !w || !x0 || bad_batch(b)) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     const hipError_t e = reset_batch(b, true, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(with_variant2(b, [](auto, auto RL) { return k_init<RL()>; }), dim3(grid_for(b->Bp, BLK)),
-                       dim3(BLK), 0, st, Dyn(*m), kw(*w), x0, b->u[0], b->x_ref, b->u_ref,
-                       (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax,
-                       b->dJ, b->B, b->Bp, b->N);
+    const dim3 grid(grid_for(b->Bp, BLK));
+    if (models)
+        hipLaunchKernelGGL(with_variant2(b, [](auto, auto RL) { return k_init<RL(), const gym_model*>; }), grid,
+                           dim3(BLK), 0, st, Dyn(*m), kw(*w), models, x0, b->u[0], b->x_ref, b->u_ref,
+                           (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax,
+                           b->dJ, b->B, b->Bp, b->N);
+    else
+        hipLaunchKernelGGL(with_variant2(b, [](auto, auto RL) { return k_init<RL()>; }), grid,
+                           dim3(BLK), 0, st, Dyn(*m), kw(*w), x0, b->u[0], b->x_ref, b->u_ref,
+                           (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax,
+                           b->dJ, b->B, b->Bp, b->N);
     return launch_status();
 }
 
-int gym_newton_init_warm(const gym_model* m, const gym_weights* w, const double* x0, const double* u_init,
-                         const int32_t* status_init, const gym_batch* b, void* s) {
+static int init_warm(const gym_model* m, const gym_model* models, const gym_weights* w, const double* x0,
+                     const double* u_init, const int32_t* status_init, const gym_batch* b, void* s) {
     if (!m || !w || !x0 || !u_init || bad_batch(b) || ((uintptr_t)u_init & 15)) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     const int T = b->N - 1;
@@ -593,11 +605,40 @@ int gym_newton_init_warm(const gym_model* m, const gym_weights* w, const double*
                        dim3(TILE_THREADS), 0, st, (const double2*)u_init, b->u[0], b->lane_map, b->B, b->Bp, T);
     int rc = launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_init_warm<U0Z(), RL()>; }),
-                       dim3(grid_for(b->Bp, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w), x0,
-                       status_init, b->lane_map, b->u[0], b->x_ref, b->u_ref, (double2*)b->x[0], b->cost, b->status,
-                       b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax, b->dJ, b->B, b->Bp, b->N);
+    const dim3 grid(grid_for(b->Bp, BLK));
+    if (models)
+        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) {
+                               return k_init_warm<U0Z(), RL(), const gym_model*>;
+                           }),
+                           grid, dim3(BLK), 0, st, Dyn(*m), kw(*w), models, x0, status_init, b->lane_map, b->u[0],
+                           b->x_ref, b->u_ref, (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll,
+                           b->gamma, b->smax, b->dJ, b->B, b->Bp, b->N);
+    else
+        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_init_warm<U0Z(), RL()>; }),
+                           grid, dim3(BLK), 0, st, Dyn(*m), kw(*w), x0,
+                           status_init, b->lane_map, b->u[0], b->x_ref, b->u_ref, (double2*)b->x[0], b->cost, b->status,
+                           b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax, b->dJ, b->B, b->Bp, b->N);
     return launch_status();
+}
+
+int gym_newton_init(const gym_model* m, const gym_weights* w, const double* x0, const gym_batch* b, void* s) {
+    return init_cold(m, nullptr, w, x0, b, s);
+}
+
+int gym_newton_init_warm(const gym_model* m, const gym_weights* w, const double* x0, const double* u_init,
+                         const int32_t* status_init, const gym_batch* b, void* s) {
+    return init_warm(m, nullptr, w, x0, u_init, status_init, b, s);
+}
+
+// a per-lane model table (gymnast_acrobot_models.h): present and 16-byte aligned (the rows are read as 16-byte pairs)
+static bool bad_models(const gym_model* models) { return !models || ((uintptr_t)models & 15); }
+// the flags no per-lane-models Newton entry point takes (as the box solve)
+static bool models_flags(const gym_batch* b) { return b && (b->flags & (GYM_FLAG_X_CKPT | GYM_FLAG_SIGMA_STREAM)); }
+
+int gym_newton_init_models(const gym_model* m, const gym_model* models, const gym_weights* w, const double* x0,
+                           const double* u_init, const int32_t* status_init, const gym_batch* b, void* s) {
+    if (bad_models(models) || models_flags(b)) return GYM_EINVAL;
+    return u_init ? init_warm(m, models, w, x0, u_init, status_init, b, s) : init_cold(m, models, w, x0, b, s);
 }
 
 // Grid caps of the post-trial kernels (grid-stride over the retry list; any cap is correct).  They launch every
@@ -810,20 +851,23 @@ int gym_newton_run(const gym_model* m, const gym_weights* w, const gym_armijo* a
 
 // gym_newton_run_box / gym_newton_run_rk4: the limited persistent kernel ``kernel_of`` picks (<U0Z, RL>) over the
 // iterations k0 .. k1-1, then the statistics after iteration k1 - 1, as gym_newton_run
-extern "C++" template <class F>
+// Args: BoxArgs, or ModelArgs with the per-lane model table of gym_newton_run_models
+extern "C++" template <class Args = BoxArgs, class F>
 static int run_limited(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
-                       const double* tau_max, int32_t k0, int32_t k1, void* s, F&& kernel_of) {
+                       const double* tau_max, int32_t k0, int32_t k1, void* s, F&& kernel_of,
+                       const gym_model* models = nullptr) {
     if (!tau_max || bad_iter_args(m, w, a, b) || k0 < 0 || k1 < k0 ||
         (b->flags & (GYM_FLAG_X_CKPT | GYM_FLAG_SIGMA_STREAM)))
         return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     if (k1 > k0) {
         TimedLaunch tl(b->timing, 8, st);
-        BoxArgs ra;
+        Args ra;
         lane_args(ra, m, w, a, b, k0);
         ra.retry_list = b->retry_list; ra.counter = b->counters;
         ra.B = b->B; ra.Bp = b->Bp; ra.N = b->N; ra.k0 = k0; ra.k1 = k1; ra.ext = 0;
         ra.tau = tau_max;
+        if constexpr (std::is_same_v<Args, ModelArgs>) ra.models = models;
         hipLaunchKernelGGL(with_variant2(b, kernel_of), dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, ra);
     }
     launch_stats(b, Range{0, b->B}, (int)k1 - 1, b->counters, b->stats, nullptr, nullptr, st);
@@ -838,6 +882,13 @@ int gym_newton_run_box(const gym_model* m, const gym_weights* w, const gym_armij
 int gym_newton_run_rk4(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
                        const double* tau_max, int32_t k0, int32_t k1, void* s) {
     return run_limited(m, w, a, b, tau_max, k0, k1, s, [](auto U0Z, auto RL) { return k_nt_run_rk4<U0Z(), RL()>; });
+}
+
+int gym_newton_run_models(const gym_model* m, const gym_model* models, const gym_weights* w, const gym_armijo* a,
+                          const gym_batch* b, const double* tau_max, int32_t k0, int32_t k1, void* s) {
+    if (bad_models(models)) return GYM_EINVAL;
+    return run_limited<ModelArgs>(m, w, a, b, tau_max, k0, k1, s,
+                                  [](auto U0Z, auto RL) { return k_nt_run_models<U0Z(), RL()>; }, models);
 }
 
 int gym_newton_tail_scratch(int32_t N, int32_t n_lanes, int32_t max_ls, int64_t* doubles_out) {
@@ -960,15 +1011,16 @@ int gym_newton_sigma(const gym_model* m, const gym_weights* w, const gym_batch* 
 
 // gym_newton_sigma_box / gym_newton_sigma_rk4: sigma1 of each lane's last limited sweep by the re-run kernel
 // ``kernel_of`` picks (<U0Z, RL>), one launch per buffer, then sigma unpacked
-extern "C++" template <class F>
+// (extra: the kernel's arguments after N, the per-lane model table of gym_newton_sigma_models)
+extern "C++" template <class F, class... X>
 static int sigma_limited(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
-                         double* sig_out, void* s, F&& kernel_of) {
+                         double* sig_out, void* s, F&& kernel_of, X... extra) {
     if (!m || !w || bad_batch(b) || !tau_max || !sig_out || (b->flags & GYM_FLAG_X_CKPT)) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     for (int parity = 0; parity < 2; ++parity) {
         hipLaunchKernelGGL(with_variant2(b, kernel_of), dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w),
                            (const double2*)b->x[parity], b->u[parity], b->x_ref, b->u_ref, b->cs, tau_max, b->n_iter,
-                           parity, b->B, b->Bp, b->N);
+                           parity, b->B, b->Bp, b->N, extra...);
         const int e = launch_status();
         if (e) return e;
     }
@@ -987,6 +1039,13 @@ int gym_newton_sigma_rk4(const gym_model* m, const gym_weights* w, const gym_bat
                          double* sig_out, void* s) {
     return sigma_limited(m, w, b, tau_max, sig_out, s,
                          [](auto U0Z, auto RL) { return k_nt_sigma_rk4<U0Z(), RL()>; });
+}
+
+int gym_newton_sigma_models(const gym_model* m, const gym_model* models, const gym_weights* w, const gym_batch* b,
+                            const double* tau_max, double* sig_out, void* s) {
+    if (bad_models(models) || models_flags(b)) return GYM_EINVAL;
+    return sigma_limited(m, w, b, tau_max, sig_out, s,
+                         [](auto U0Z, auto RL) { return k_nt_sigma_models<U0Z(), RL()>; }, models);
 }
 
 static int sweep_grid(int64_t Bp, int G) {

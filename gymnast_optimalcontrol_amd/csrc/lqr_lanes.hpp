@@ -172,14 +172,35 @@ __device__ __forceinline__ void lqr_lane_stage(const Dyn& m, double2 xa, double2
     b3 = m.h * J.bc3;
 }
 
+// The model of a closed loop's plant step x_{t+1} = RK4(x_t, u_t) (DESIGN 4.8).  Without a table it is the design
+// model m itself, by reference, so a kernel instantiated without one is the kernel it was before tables existed.  With
+// one it is row `row` of a table of gym_model (gym::model_row, read once per thread before the time loop); dt is the
+// design model's.  A thread that is not `valid` (padding) reads nothing and gets the design model.  The per-lane gain
+// sweep (k_lqr_lane_gains) takes its design model the same way from a (B) table.
+__device__ __forceinline__ const Dyn& lane_plant(const Dyn& m, int64_t, bool) { return m; }
+__device__ __forceinline__ Dyn lane_plant(const Dyn& m, int64_t row, bool valid, const gym_model* rows) {
+    if (!valid) return m;
+    return gym::model_row(m, rows, row);
+}
+// the design model of lane l in k_lqr_lane_gains: m itself, or with a (B) table row l (padding lanes: m)
+__device__ __forceinline__ const Dyn& lane_design(const Dyn& m, int64_t) { return m; }
+__device__ __forceinline__ Dyn lane_design(const Dyn& m, int64_t l, const gym_model* rows, int64_t B) {
+    return lane_plant(m, l, l < B, rows);
+}
+
 // solve_LQR_tracking per lane: reverse time over the packed trajectory, row 1 of every K_t to the K1 stream.
 // Stage t - 1's operands are loaded (non-temporal: read once) while stage t is computed.  Padding lanes run on
 // their zero trajectory (finite everywhere) and fill their own slots of K1.  grid Bp / 64.
-__global__ __launch_bounds__(BLK) void k_lqr_lane_gains(Dyn m, Sym4 Q, Sym4 QT, double r11,
+// k<>: every lane is designed on m; k<const gym_model*, int64_t>: the pack Md is the two parameters after m, a (B)
+// table of design models in the caller's lane order and B: lane l linearises on row l (lane_plant), padding lanes of a
+// ragged group on m.  m.h stays m's.
+template <class... Md>
+__global__ __launch_bounds__(BLK) void k_lqr_lane_gains(Dyn m, Md... models, Sym4 Q, Sym4 QT, double r11,
                                                         const double2* __restrict__ xs, const double* __restrict__ us,
                                                         double2* __restrict__ ks, int64_t Bp, int N) {
     const int64_t l = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int T = N - 1;
+    decltype(auto) dm = lane_design(m, l, models...);
     Sym4 P = QT;
     double2 xa = ld_nt(xs + wix(T - 1, 0, 2, l, Bp)), xb = ld_nt(xs + wix(T - 1, 1, 2, l, Bp));
     double u1 = ld_nt(us + pix(T - 1, 1, 2, l, Bp));
@@ -191,7 +212,7 @@ __global__ __launch_bounds__(BLK) void k_lqr_lane_gains(Dyn m, Sym4 Q, Sym4 QT, 
         xb = ld_nt(xs + wix(tn, 1, 2, l, Bp));
         u1 = ld_nt(us + pix(tn, 1, 2, l, Bp));
         double a2[4], a3[4], b2, b3, k[4];
-        lqr_lane_stage(m, ca, cb, cu, a2, a3, b2, b3);
+        lqr_lane_stage(dm, ca, cb, cu, a2, a3, b2, b3);
         lqr_lane_step(a2, a3, b2, b3, m.h, r11, Q, P, k);
         st_nt(ks + wix(t, 0, 2, l, Bp), k[0], k[1]);
         st_nt(ks + wix(t, 1, 2, l, Bp), k[2], k[3]);
@@ -204,20 +225,6 @@ __device__ __forceinline__ double lqr_lane_feedback(double2 ka, double2 kb, doub
                                                     double d3) {
 #pragma clang fp contract(on)
     return f1 + (((ka.x * d0 + ka.y * d1) + kb.x * d2) + kb.y * d3);
-}
-
-// The model of a closed loop's plant step x_{t+1} = RK4(x_t, u_t) (DESIGN 4.8).  Without a table it is the design
-// model m itself, by reference, so a kernel instantiated without one is the kernel it was before tables existed.  With
-// one it is row `row` of a (B,P) table of gym_model (64 bytes a row, 16-byte aligned, read once per thread before the
-// time loop), made a Dyn by the constructor the host uses for m, so bb, dad, h2 and h6 are the same single-rounded
-// operations on both sides; dt is the design model's.  A thread that is not `valid` (padding) reads nothing and gets
-// the design model.  The nine coefficients are then per-thread registers, not scalars.
-__device__ __forceinline__ const Dyn& lane_plant(const Dyn& m, int64_t, bool) { return m; }
-__device__ __forceinline__ Dyn lane_plant(const Dyn& m, int64_t row, bool valid, const gym_model* rows) {
-    if (!valid) return m;
-    const double2* r = reinterpret_cast<const double2*>(rows + row);
-    const double2 ab = r[0], dg = r[1], gf = r[2], fd = r[3];
-    return Dyn(gym_model{ab.x, ab.y, dg.x, dg.y, gf.x, gf.y, fd.x, m.h});
 }
 
 // simulate_tracking per lane and perturbed start: B P threads, a wavefront = 64 consecutive lanes at one start index

@@ -574,7 +574,9 @@ __device__ __forceinline__ void backward_solver_lane(const Dyn& m, const KW& w,
 // 6, so that no set is copied -- a copy of a loading register waits for its load).  Same per-stage arithmetic
 // as backward_solver_lane (step = jacobian + step_j): the same bits.
 // BOX (newton_box.hpp): the sweep of the box solver with the lane's torque limit tau, |u1_t| <= tau on every stage.
-template <bool U0Z, int OUT, bool BOX = false>
+// LM (newton_models.hpp): the stage Jacobians on m, this thread's own model (its nine coefficients in VGPRs); without
+// it m is not read and every constant is kernarg_consts()'s.  dt and the weights are kernarg_consts()'s either way.
+template <bool U0Z, int OUT, bool BOX = false, bool LM = false>
 __device__ __forceinline__ void backward_solver_lane_ilp(const Dyn& m, const KW& w,
                                                          const double2* __restrict__ x, const double* __restrict__ u,
                                                          const double* __restrict__ xr, const double* __restrict__ ur,
@@ -598,8 +600,12 @@ __device__ __forceinline__ void backward_solver_lane_ilp(const Dyn& m, const KW&
         q.u1 = bld1(rU, o1, plane);
     };
     auto jac = [&](const SweepStage& q) {
-        const KArgs ka = kernarg_consts();
-        return gym::jacobian(ka.m, q.xa.x, q.xa.y, q.xb.x, q.xb.y, q.u1, pk);
+        if constexpr (LM) {
+            return gym::jacobian(m, q.xa.x, q.xa.y, q.xb.x, q.xb.y, q.u1, pk);
+        } else {
+            const KArgs ka = kernarg_consts();
+            return gym::jacobian(ka.m, q.xa.x, q.xa.y, q.xb.x, q.xb.y, q.u1, pk);
+        }
     };
     // stage t: c = its streams, Jc = its Jacobian; n = stage t-1's streams (landed), f <- stage t-2's
     auto stage = [&](const SweepStage& c, const SweepStage& n, SweepStage& f, const gym::Jac& Jc, gym::Jac& Jn,

@@ -450,8 +450,15 @@ __global__ __launch_bounds__(TILE_THREADS) void k_gather_pack_u(const double2* _
 // Warm start (gym_newton_init_warm): k_init's reset, with x[0] rolled out from x0 under the caller's controls
 // (already packed into u[0]) and each lane's status taken from status_init.  Internal lane l takes row map[l] of x0
 // and status_init (NULL: l); per-lane references are indexed by the internal lane, as everywhere.
-template <bool U0Z, bool RL>
-__global__ __launch_bounds__(BLK) void k_init_warm(Dyn m, KW w, const double* __restrict__ x0,
+// Both init kernels: k<...>: every lane rolls out on m; k<..., const gym_model*>: the pack Md is the one parameter
+// after w, the (Bp) table of per-lane models in internal lane order (gym_newton_init_models): lane l rolls out on row
+// l (gym::model_row), dt staying m's.
+__device__ __forceinline__ const Dyn& init_model(const Dyn& m, int64_t) { return m; }
+__device__ __forceinline__ Dyn init_model(const Dyn& m, int64_t l, const gym_model* rows) {
+    return gym::model_row(m, rows, l);
+}
+template <bool U0Z, bool RL, class... Md>
+__global__ __launch_bounds__(BLK) void k_init_warm(Dyn m, KW w, Md... models, const double* __restrict__ x0,
                                                    const int32_t* __restrict__ status_init,
                                                    const int64_t* __restrict__ map, const double* __restrict__ u,
                                                    const double* __restrict__ xr, const double* __restrict__ ur,
@@ -473,13 +480,14 @@ __global__ __launch_bounds__(BLK) void k_init_warm(Dyn m, KW w, const double* __
     // lane (GYM_ACTIVE, GYM_MAX_ITERS) or out of contract, and iterates
     const int32_t s_in = status_init ? status_init[row] : (int32_t)GYM_ACTIVE;
     status[l] = (s_in == GYM_CONVERGED || s_in == GYM_LS_FAILED) ? s_in : (int32_t)GYM_ACTIVE;
-    cost[l] = rollout_warm<U0Z>(m, w, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
+    decltype(auto) lm = init_model(m, l, models...);
+    cost[l] = rollout_warm<U0Z>(lm, w, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
                                 lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), xn, l, Bp, N, x0[4 * row + 0],
                                 x0[4 * row + 1], x0[4 * row + 2], x0[4 * row + 3]);
 }
 
-template <bool RL = false>
-__global__ __launch_bounds__(BLK) void k_init(Dyn m, KW w, const double* __restrict__ x0,
+template <bool RL = false, class... Md>
+__global__ __launch_bounds__(BLK) void k_init(Dyn m, KW w, Md... models, const double* __restrict__ x0,
                                               const double* __restrict__ u, const double* __restrict__ xr,
                                               const double* __restrict__ ur, double2* __restrict__ xn,
                                               double* __restrict__ cost, int32_t* __restrict__ status,
@@ -496,7 +504,8 @@ __global__ __launch_bounds__(BLK) void k_init(Dyn m, KW w, const double* __restr
         return;
     }
     status[l] = GYM_ACTIVE;
-    cost[l] = rollout_ref<false>(m, w, nullptr, u, nullptr, nullptr, lane_ref<RL>(xr, l, 4 * (int64_t)N),
+    decltype(auto) lm = init_model(m, l, models...);
+    cost[l] = rollout_ref<false>(lm, w, nullptr, u, nullptr, nullptr, lane_ref<RL>(xr, l, 4 * (int64_t)N),
                                  lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), xn, nullptr, 0.0, l, Bp, N,
                                  x0[4 * l + 0], x0[4 * l + 1], x0[4 * l + 2], x0[4 * l + 3]);
 }

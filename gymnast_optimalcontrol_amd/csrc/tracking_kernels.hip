@@ -23,6 +23,7 @@
 #endif
 #include "acrobot_device.hpp"
 #include "gymnast_acrobot.h"
+#include "gymnast_acrobot_models.h"
 
 using gym::Dyn;
 
@@ -279,10 +280,11 @@ int gym_lqr_lanes_workspace(int64_t B, int32_t N, int64_t* bytes_out) {
     return 0;
 }
 
-// solve_LQR_tracking (trajectory_tracking.py:170-203) per lane
-int gym_lqr_lanes_gains(const gym_model* m, const double* x_opt, const double* u_opt, int64_t B, int32_t N,
-                        const double Q[16], const double R[4], const double QT[16], void* ws, int64_t ws_bytes,
-                        double* K_out, void* s) {
+// solve_LQR_tracking (trajectory_tracking.py:170-203) per lane; models: the (B) table of per-lane design models, or
+// null for m on every lane
+static int lanes_gains_launch(const gym_model* m, const gym_model* models, const double* x_opt, const double* u_opt,
+                              int64_t B, int32_t N, const double Q[16], const double R[4], const double QT[16], void* ws,
+                              int64_t ws_bytes, double* K_out, void* s) {
     if (!m || !x_opt || !u_opt || !Q || !R || !QT || !ws || !lanes_sizes_ok(B, N) || !box_weights_ok(R) ||
         !lanes_sym(Q) || !lanes_sym(QT))
         return GYM_EINVAL;
@@ -290,10 +292,29 @@ int gym_lqr_lanes_gains(const gym_model* m, const double* x_opt, const double* u
     if (ws_bytes < w.lo.bytes || w.groups * w.ntx > ((int64_t)1 << 31) - 1) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     lanes_pack(w, x_opt, u_opt, B, st);
-    hipLaunchKernelGGL(k_lqr_lane_gains, dim3((unsigned)w.groups), dim3(BLK), 0, st, Dyn(*m), sym4(Q), sym4(QT), R[3],
-                       w.xs, w.us, w.ks, w.lo.Bp, (int)N);
+    if (models)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lqr_lane_gains<const gym_model*, int64_t>), dim3((unsigned)w.groups),
+                           dim3(BLK), 0, st, Dyn(*m), models, B, sym4(Q), sym4(QT), R[3], w.xs, w.us, w.ks, w.lo.Bp,
+                           (int)N);
+    else
+        hipLaunchKernelGGL(k_lqr_lane_gains<>, dim3((unsigned)w.groups), dim3(BLK), 0, st, Dyn(*m), sym4(Q), sym4(QT),
+                           R[3], w.xs, w.us, w.ks, w.lo.Bp, (int)N);
     lanes_unpack_gains(w, K_out, B, st);
     return launch_status();
+}
+
+int gym_lqr_lanes_gains(const gym_model* m, const double* x_opt, const double* u_opt, int64_t B, int32_t N,
+                        const double Q[16], const double R[4], const double QT[16], void* ws, int64_t ws_bytes,
+                        double* K_out, void* s) {
+    return lanes_gains_launch(m, nullptr, x_opt, u_opt, B, N, Q, R, QT, ws, ws_bytes, K_out, s);
+}
+
+// the same with lane l linearised on models[l] (gymnast_acrobot_models.h)
+int gym_lqr_lanes_gains_models(const gym_model* m, const gym_model* models, const double* x_opt, const double* u_opt,
+                               int64_t B, int32_t N, const double Q[16], const double R[4], const double QT[16],
+                               void* ws, int64_t ws_bytes, double* K_out, void* s) {
+    if (!plant_ok(models)) return GYM_EINVAL;
+    return lanes_gains_launch(m, models, x_opt, u_opt, B, N, Q, R, QT, ws, ws_bytes, K_out, s);
 }
 
 // simulate_tracking (trajectory_tracking.py:206-216) per lane and perturbed start; plant: the (B,P) table of the

@@ -94,6 +94,11 @@ class PlantTables:
                              "b = m2 l1 lc2, d = I2 + lc2^2 m2)") from e
         return torch.as_tensor(rows.reshape(B, P, 8), device=self.device)
 
+    def model_table(self, models, B: int) -> torch.Tensor:
+        """The (B,8) float64 device table of per-lane models (BatchedNewtonSolver's ``models``, lqr_lanes_gains'
+        ``models``): plant_table's call and upload with one row per lane, check_models' forms and refusals."""
+        return self.plant_table(check_models(models, B, self.params), B, 1).reshape(B, 8)
+
 
 class AcrobotEngine(PlantTables):
     """Launchers for one acrobot parameter set on one HIP device."""
@@ -531,16 +536,22 @@ class AcrobotEngine(PlantTables):
         """The caller-owned workspace of gym_lqr_lanes_gains / gym_lqr_lanes_rollout for B lanes of N knots."""
         return self._workspace(None, "gym_lqr_lanes_workspace", B, N)[0]
 
-    def lqr_lanes_gains(self, x_opt, u_opt, Q, R, QT, gains: bool = True, ws=None):
+    def lqr_lanes_gains(self, x_opt, u_opt, Q, R, QT, gains: bool = True, ws=None, models=None):
         """gym_lqr_lanes_gains: solve_LQR_tracking per lane along x_opt (B,N,4), u_opt (B,N-1,2).  Returns (ws, K):
-        the filled workspace lqr_lanes_rollout takes, and K (B,N-1,2,4) on the device (None unless ``gains``)."""
+        the filled workspace lqr_lanes_rollout takes, and K (B,N-1,2,4) on the device (None unless ``gains``).
+        ``models``: a model_table (B,8); lane b is then linearised on its own row (gym_lqr_lanes_gains_models)."""
         x_opt = self.t(x_opt); u_opt = self.t(u_opt)
         B, N = check_lane_trajectories(x_opt, u_opt)
         Rh = check_diagonal_R(R, "per-lane LQR tracking")
         Qh, QTh = check_sym_weight(Q, "Q"), check_sym_weight(QT, "QT")
         ws, ws_bytes = self._workspace(ws, "gym_lqr_lanes_workspace", B, N)
         K = self._buf(B, N - 1, 2, 4, want=gains)
-        self._call("gym_lqr_lanes_gains", self.model, x_opt, u_opt, B, N, Qh, Rh, QTh, ws, ws_bytes, K)
+        if models is None:
+            self._call("gym_lqr_lanes_gains", self.model, x_opt, u_opt, B, N, Qh, Rh, QTh, ws, ws_bytes, K)
+        else:
+            check_model_table(models, B)
+            self._call("gym_lqr_lanes_gains_models", self.model, models, x_opt, u_opt, B, N, Qh, Rh, QTh, ws, ws_bytes,
+                       K)
         return ws, K
 
     def lqr_lanes_rollout(self, ws, x0, N: int, trajectories: bool = True, plant=None):
@@ -788,6 +799,23 @@ def check_plant(plant, B: int, P: int, own_params) -> np.ndarray:
     if not np.isfinite(out).all():
         raise ValueError("plant parameters must be finite")
     return out
+
+
+def check_models(models, B: int, own_params) -> np.ndarray:
+    """The parameters of every lane's own model, (B,11) float64 in params.PARAM_NAMES order: check_plant with one plant
+    per lane (P = 1), so a set number, a dict of names to scalars or (B,) arrays, (11,), (B,11) or (B,1,11) such as
+    sample_plants(B, 1), with check_plant's refusals in its words."""
+    if isinstance(models, dict):       # (B,) arrays are per lane: one column of the (B,1) check_plant broadcasts to
+        models = {k: (np.asarray(v, dtype=np.float64).reshape(-1, 1) if np.ndim(v) == 1 and k in PARAM_NAMES else v)
+                  for k, v in models.items()}
+    return check_plant(models, B, 1, own_params).reshape(int(B), 11)
+
+
+def check_model_table(table, B: int):
+    """A per-lane model table as AcrobotEngine.model_table makes it: a float64 tensor (B,8), one gym_model per lane."""
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float64 or tuple(table.shape) != (B, 8):
+        raise ValueError(f"models must be a model_table ({B},8) float64 tensor, got "
+                         f"{getattr(table, 'dtype', type(table).__name__)} {tuple(getattr(table, 'shape', ()))}")
 
 
 def check_plant_table(table, B: int, P: int):

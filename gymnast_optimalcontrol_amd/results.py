@@ -39,16 +39,20 @@ class SolveResult:
     tail_iterations: int = 0                # outer iterations the tail ran (its slowest lane's, up to the last one)
     tau_max: torch.Tensor | None = None     # (B,) per-lane torque limits of a limited solve (None: no limit)
     linearization: str = "euler"            # the sweep's linearisation: "euler" (the reference's) or "rk4"
+    models: np.ndarray | None = None        # (B,11) host: the parameter set each lane was planned on (None: the engine's)
 
     def save_npz(self, path, t=None, dt: float = DT):
         """Write the per-lane results as one .npz in the reference's wire format (main.py:74-79, np.savez(x=, u=,
         t=)): x (B,N,4), u (B,T,2), t (N,) = arange(N) * dt unless given, plus cost, status, n_iter, gamma,
         n_rollouts, K and sigma, which load_checkpoint / BatchedNewtonSolver.resume continue from, and
-        ``linearization`` where it is not the reference's "euler" (a file without it is an Euler solve's).  Host I/O
+        ``linearization`` where it is not the reference's "euler" (a file without it is an Euler solve's) and
+        ``models`` (B,11) where the lanes were planned on their own (a file without it: on the engine's).  Host I/O
         only: tensors on any device."""
         a = {k: getattr(self, k).detach().cpu().numpy() for k in CHECKPOINT_KEYS}
         if self.linearization != "euler":
             a["linearization"] = np.array(self.linearization)
+        if self.models is not None:
+            a["models"] = np.asarray(self.models, dtype=np.float64)
         N = a["x"].shape[1]
         a["t"] = np.arange(N) * float(dt) if t is None else np.asarray(t, dtype=np.float64)
         if a["t"].shape != (N,):
@@ -78,8 +82,11 @@ class SolveResult:
         """LQR tracking of every lane's own result (trajectory_tracking.LQR_tracking_lanes on this result's x, u):
         x0 (B,4) or (B,P,4) perturbed starts, default x[:, 0] + dx0 with dx0 (4,), (B,4) or (B,P,4) (default: no
         perturbation).  Keyword arguments go to LQR_tracking_lanes, ``plant=`` among them: a mismatched plant per closed
-        loop, e.g. ``plant=trajectory_tracking.sample_plants(B, P)`` for dx0 (B,P,4).  Returns its LqrLanesResult."""
+        loop, e.g. ``plant=trajectory_tracking.sample_plants(B, P)`` for dx0 (B,P,4).  A result planned on per-lane
+        models passes them on (``models=self.models`` unless given): every lane's gains are designed on, and without
+        ``plant=`` its closed loops simulated on, the model it was planned for.  Returns its LqrLanesResult."""
         from . import trajectory_tracking as tt
+        kw.setdefault("models", self.models)
         return tt.LQR_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
 
     def track_mpc(self, x0=None, dx0=None, **kw):
@@ -90,8 +97,19 @@ class SolveResult:
         reference's) every lane's closed loop keeps |u| <= tau_max and the result is an MpcBoxLanesResult.
         ``tau_max=trajectory_tracking.TorqueLimit(18.0)`` adds the projected-Newton fallback: a QP whose active set
         has not settled after max_qp_iters sweeps is finished by it, qp_iters counts both phases and unconverged only
-        the QPs that neither phase finished."""
+        the QPs that neither phase finished.  The MPC trackers design on the engine's model only: on a result planned
+        on per-lane models this raises NotImplementedError unless ``models=None`` is passed to say that the engine's
+        model is meant."""
         from . import trajectory_tracking as tt
+        if "models" in kw:
+            if kw.pop("models") is not None:
+                raise NotImplementedError("per-lane MPC tracking designs on the engine's model only; use track_lqr "
+                                          "for a design per lane")
+        elif self.models is not None:
+            raise NotImplementedError(
+                "this result was planned on per-lane models and the MPC trackers design on the engine's model only: "
+                "use track_lqr (which designs each lane on its own model), or pass models=None to track_mpc to say "
+                "that the engine's model is meant")
         return tt.MPC_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
 
 
@@ -112,6 +130,7 @@ class Checkpoint:
     K: torch.Tensor          # (B,T,2,4)
     sigma: torch.Tensor      # (B,T,2)
     linearization: str = "euler"   # the sweep the iterates come from; resume() on a solver of the other is refused
+    models: np.ndarray | None = None   # (B,11) per-lane parameter sets of the solve; resume() needs the same bits
 
 
 def load_checkpoint(path, device="cpu") -> Checkpoint:
@@ -146,4 +165,14 @@ def load_checkpoint(path, device="cpu") -> Checkpoint:
                 raise ValueError(f"{path}: '{k}' has shape {v.shape}, expected {full[k].shape}")
             full[k] = v
     return Checkpoint(**{k: torch.as_tensor(v).to(device) for k, v in full.items()},
-                      linearization=str(a["linearization"]) if "linearization" in a else "euler")
+                      linearization=str(a["linearization"]) if "linearization" in a else "euler",
+                      models=_ckpt_models(a, B, path))
+
+
+def _ckpt_models(a, B, path):
+    if "models" not in a:
+        return None
+    m = np.ascontiguousarray(a["models"], dtype=np.float64)
+    if m.shape != (B, 11):
+        raise ValueError(f"{path}: 'models' has shape {m.shape}, expected {(B, 11)}")
+    return m

@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib, placement
-from .engine import AcrobotEngine, padded, F64
+from .engine import AcrobotEngine, check_models, padded, F64
 from .host_loop import STAT_FIELDS, morton_order, newton_loop, run_loop, tail_loop  # noqa: F401
 from .params import MAX_LINE_SEARCH_ITERS
 from .placement import PlacementPool
@@ -96,7 +96,7 @@ class BatchedNewtonSolver:
                  capture_sigma=(0, 1, 2), tail_lanes: int | None = None, tail_chunk: int = 128,
                  compact: bool | None = None, world_size: int = 1, cand_slots: int | None = None,
                  arena=False, placement_trials: int | None = None, tau_max=None,
-                 linearization: str = "euler"):
+                 linearization: str = "euler", models=None):
         if B <= 0:
             raise ValueError("batch must hold at least one lane")
         engine.weights.require_gain_solvable()
@@ -108,7 +108,7 @@ class BatchedNewtonSolver:
             raise ValueError("max_ls must be >= 1")
         self._set_u0_flag(u0_zero)
         auto_schedule = pipeline is None and persistent is None
-        pipeline, persistent = self._set_limited(tau_max, linearization, pipeline, persistent, checkpoint)
+        pipeline, persistent = self._set_limited(tau_max, linearization, models, pipeline, persistent, checkpoint)
         self._choose_schedule(pipeline, persistent, schedule_lanes, checkpoint, chunk, reorder, split_waves)
         self._set_capture(capture_lanes, capture_every, capture_sigma)
         st, placement_trials = self._alloc_streams(arena, placement_trials, auto_schedule)
@@ -157,22 +157,33 @@ class BatchedNewtonSolver:
         self.u0_zero = ref_u0_zero if u0_zero is None else bool(u0_zero)
         self._u0_cleared = False   # the flag is off for one warm-started solve whose u_init has tau1 != 0 (init)
 
-    def _set_limited(self, tau_max, linearization, pipeline, persistent, checkpoint):
+    def _set_limited(self, tau_max, linearization, models, pipeline, persistent, checkpoint):
         """The torque limit |tau2| <= tau_max of a limited solve (a number or (B,) per-lane limits, each positive, inf
-        allowed) and the sweep's linearisation: "euler" (the reference's A_d = I + dt A_c) or "rk4" (the exact
-        Jacobians of the RK4 step).  A solver with either runs the persistent loop on its own kernel
-        (gym_newton_run_box / gym_newton_run_rk4) and nothing else: no pipeline, tail, compaction, low-occupancy
-        switch, checkpointing or candidate scratch.  "rk4" without a limit passes +inf limits to that kernel and
-        reports none.  Returns (pipeline, persistent) as _choose_schedule takes them."""
+        allowed), the sweep's linearisation: "euler" (the reference's A_d = I + dt A_c) or "rk4" (the exact
+        Jacobians of the RK4 step), and per-lane models (check_models' forms: lane b is planned on
+        models[b]).  A solver with any of them runs the persistent loop on its own kernel
+        (gym_newton_run_box / gym_newton_run_rk4 / gym_newton_run_models) and nothing else: no pipeline, tail,
+        compaction, low-occupancy switch, checkpointing or candidate scratch.  "rk4" or models without a limit pass
+        +inf limits to that kernel and report none.  Returns (pipeline, persistent) as _choose_schedule takes them."""
         if linearization not in ("euler", "rk4"):
             raise ValueError(f'linearization must be "euler" or "rk4", got {linearization!r}')
         self.linearization = linearization
         self._run_fn, self._sigma_fn = (("gym_newton_run_rk4", "gym_newton_sigma_rk4") if linearization == "rk4" else
                                         ("gym_newton_run_box", "gym_newton_sigma_box"))
         self._tau_in = self.tau_buf = None
-        if tau_max is None and linearization == "euler":
+        self.models = self._models_in = self.models_buf = None
+        if models is not None:
+            if linearization == "rk4":
+                raise ValueError('per-lane models (models=) do not combine with linearization="rk4"')
+            self.models = check_models(models, self.B, self.eng.params)        # (B,11) host, the caller's order
+            self._models_in = self.eng.model_table(self.models, self.B)          # (B,8) device, the caller's order
+            pad = self._models_in[-1:].expand(self.Bp - self.B, -1)              # padding lanes: a valid row
+            self.models_buf = torch.cat([self._models_in, pad]).contiguous()    # internal order (init)
+            self._run_fn, self._sigma_fn = "gym_newton_run_models", "gym_newton_sigma_models"
+        if tau_max is None and linearization == "euler" and models is None:
             return pipeline, persistent
-        self._limited = "a torque-limited solve (tau_max)" if tau_max is not None else 'linearization="rk4"'
+        self._limited = ("a torque-limited solve (tau_max)" if tau_max is not None else
+                         'linearization="rk4"' if models is None else "per-lane models (models=)")
         if pipeline or checkpoint or persistent is False:
             raise ValueError(f"{self._limited} runs the persistent schedule only: no pipeline=True, "
                              "persistent=False or checkpoint=True")
@@ -361,14 +372,17 @@ class BatchedNewtonSolver:
 
     # --- launches and streams --------------------------------------------------------------
     def _launch(self, name, *args, pre=(), model=True, weights=None, armijo=False, batch=True, stream=True,
-                check=True):
-        """Call the library's ``name`` as (model, weights[, armijo], *pre, batch, *args, stream) -- the keywords drop
-        or add a part (``weights`` follows ``model`` unless given) -- and raise on a non-zero return code unless
-        ``check`` is off.  Returns the code."""
+                check=True, table=False):
+        """Call the library's ``name`` as (model[, models], weights[, armijo], *pre, batch, *args, stream) -- the
+        keywords drop or add a part (``weights`` follows ``model`` unless given; ``table``: the per-lane model table
+        of the ..._models entry points) -- and raise on a non-zero return code unless ``check`` is off.  Returns the
+        code."""
         eng = self.eng
         a = []
         if model:
             a.append(C.byref(eng.model))
+        if table:
+            a.append(self.models_buf.data_ptr())
         if model if weights is None else weights:
             a.append(C.byref(eng._w))
         if armijo:
@@ -547,10 +561,14 @@ class BatchedNewtonSolver:
             self.tau_buf[:self.B] = self._tau_in if _ref_perm is None else self._tau_in[_ref_perm]
             if u_init is not None and bool((u_init[..., 1].abs() > self._tau_in[:, None]).any().item()):
                 raise ValueError("u_init leaves the torque limit: |u_init[:, :, 1]| <= tau_max must hold per lane")
+        if self.models_buf is not None:   # and the per-lane models
+            self.models_buf[:self.B] = self._models_in if _ref_perm is None else self._models_in[_ref_perm]
         self._x0 = x0
         if self._pl is not None and self._pl.start(self):
             self._end_placement()
-        if u_init is None:
+        if u_init is None and self.models_buf is not None:
+            self._launch("gym_newton_init_models", pre=(x0.data_ptr(), None, None), table=True)
+        elif u_init is None:
             self._launch("gym_newton_init", pre=(x0.data_ptr(),))
         else:
             if self.u0_zero and bool((u_init[..., 0] != 0).any().item()):
@@ -560,7 +578,9 @@ class BatchedNewtonSolver:
             # finalize's use of the field)
             self.batch.lane_map = None if _lane_map is None else _lane_map.data_ptr()
             try:
-                self._launch("gym_newton_init_warm", pre=(x0.data_ptr(), u_init.data_ptr(), _lib.ptr(status_init)))
+                self._launch("gym_newton_init_models" if self.models_buf is not None else "gym_newton_init_warm",
+                             pre=(x0.data_ptr(), u_init.data_ptr(), _lib.ptr(status_init)),
+                             table=self.models_buf is not None)
             finally:
                 self.batch.lane_map = None
         self.k = 0
@@ -575,7 +595,8 @@ class BatchedNewtonSolver:
     def _run(self, k0: int, k1: int):
         self.launches["run"] += 1
         if self.tau_buf is not None:
-            self._launch(self._run_fn, self.tau_buf.data_ptr(), int(k0), int(k1), armijo=True)
+            self._launch(self._run_fn, self.tau_buf.data_ptr(), int(k0), int(k1), armijo=True,
+                         table=self.models_buf is not None)
         else:
             self._launch("gym_newton_run", int(k0), int(k1), armijo=True)
 
@@ -696,7 +717,7 @@ class BatchedNewtonSolver:
         x, u, K, s = (torch.empty((B, *sh), dtype=F64, device=dev) for sh in ((N, 4), (T, 2), (T, 2, 4), (T, 2)))
         if self.tau_buf is not None:   # the limited sigma: the box sweep re-run, never the unlimited one
             self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), None)
-            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr())
+            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr(), table=self.models_buf is not None)
         else:
             self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), s.data_ptr())
         return x, u, K, s
@@ -757,7 +778,7 @@ class BatchedNewtonSolver:
             return s
         s = torch.empty((self.B, self.T, 2), dtype=F64, device=self.eng.device)
         if self.tau_buf is not None:
-            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr())
+            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr(), table=self.models_buf is not None)
         else:
             self._launch("gym_newton_sigma", s.data_ptr())
         return s
@@ -853,6 +874,8 @@ class BatchedNewtonSolver:
             self.ur_buf[moved] = self.ur_buf[src]
         if self.tau_buf is not None:
             self.tau_buf[moved] = self.tau_buf[src]
+        if self.models_buf is not None:
+            self.models_buf[moved] = self.models_buf[src]
         order = self.lane_order if self.lane_order is not None else torch.arange(B, device=dev)
         self.lane_order = order[perm[:B]]
         self.compactions += 1
@@ -940,7 +963,8 @@ class BatchedNewtonSolver:
                            tail_from_iteration=self.tail_from, tail_iterations=int(self.tail_iters),
                            compactions=int(self.compactions), lowocc_lane_iterations=int(lowocc),
                            tau_max=None if self._tau_in is None else self._tau_in.clone(),
-                           linearization=self.linearization, **res)
+                           linearization=self.linearization,
+                           models=None if self.models is None else self.models.copy(), **res)
 
     def resume(self, ckpt: Checkpoint, max_iters: int, **solve_kw) -> SolveResult:
         """Continue a checkpoint (load_checkpoint) for up to ``max_iters`` further iterations:
@@ -958,6 +982,10 @@ class BatchedNewtonSolver:
         if ckpt.linearization != self.linearization:   # another sweep: not the same solve continued
             raise ValueError(f'the checkpoint was solved with linearization="{ckpt.linearization}", this solver has '
                              f'"{self.linearization}"')
+        if (ckpt.models is None) != (self.models is None) or (
+                self.models is not None and ckpt.models.tobytes() != self.models.tobytes()):
+            raise ValueError("the checkpoint's per-lane models differ from this solver's (models=): another plant "
+                             "per lane is not the same solve continued")
         c = {k: getattr(ckpt, k).to(dev) for k in CHECKPOINT_KEYS}
         if c["x"].ndim != 3 or c["x"].shape[0] != self.B or c["x"].shape[1] != self.N:
             raise ValueError(f"the checkpoint holds x {tuple(c['x'].shape)}, this solver ({self.B},{self.N},4)")
@@ -980,14 +1008,16 @@ def newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, g
                        max_ls=MAX_LINE_SEARCH_ITERS, engine: AcrobotEngine | None = None, hist_len=0,
                        reduce_stats=None, pipeline: bool | None = None,
                        persistent: bool | None = None, capture_lanes=None, u_init=None, tau_max=None,
-                       linearization: str = "euler") -> SolveResult:
+                       linearization: str = "euler", models=None) -> SolveResult:
     """Batched newton_Algorithm: x0 (B,4) -> SolveResult (device tensors).  ``u_init`` (B,T,2): start from these
     controls instead of u = 0 (BatchedNewtonSolver.init).  ``tau_max`` (a number or (B,)): the torque-limited solve
     (BatchedNewtonSolver's tau_max).  ``linearization``: "euler" (the reference's) or "rk4" (the exact Jacobians of
-    the RK4 step, BatchedNewtonSolver's linearization)."""
+    the RK4 step, BatchedNewtonSolver's linearization).  ``models``: one parameter set per lane, lane b planned on
+    models[b] (BatchedNewtonSolver's models)."""
     eng = engine or AcrobotEngine()
     x0 = eng.t(x0).reshape(-1, 4)
     solver = BatchedNewtonSolver(eng, x_ref, u_ref, x0.shape[0], tol=tol, beta=beta, c=c, gamma_0=gamma_0,
                                  max_ls=max_ls, hist_len=hist_len, pipeline=pipeline, persistent=persistent,
-                                 capture_lanes=capture_lanes, tau_max=tau_max, linearization=linearization)
+                                 capture_lanes=capture_lanes, tau_max=tau_max, linearization=linearization,
+                                 models=models)
     return solver.solve(x0, max_iters, reduce_stats=reduce_stats, u_init=u_init)

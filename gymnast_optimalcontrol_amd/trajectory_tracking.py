@@ -42,7 +42,7 @@ import torch
 
 from . import _lib
 from . import dynamics as _dyn
-from .engine import check_box, check_lane_starts, check_lane_trajectories, check_plant, check_window
+from .engine import check_box, check_lane_starts, check_lane_trajectories, check_models, check_plant, check_window
 from .params import PARAM_NAMES, PARAM_SETS
 from .dynamics import dt, ns, ni  # noqa: F401  (the reference module's namespace, trajectory_tracking.py:3)
 
@@ -231,8 +231,8 @@ def lqr_gains_lanes(x_opt, u_opt, Q=Q_REG, R=R_REG, QT=QT_REG) -> torch.Tensor:
     return eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=True)[1]
 
 
-def LQR_tracking_lanes(x_opt, u_opt, x0, plant=None, *, trajectories: bool = True, gains: bool = True, Q=Q_REG,
-                       R=R_REG, QT=QT_REG) -> LqrLanesResult:
+def LQR_tracking_lanes(x_opt, u_opt, x0, plant=None, models=None, *, trajectories: bool = True, gains: bool = True,
+                       Q=Q_REG, R=R_REG, QT=QT_REG) -> LqrLanesResult:
     """LQR tracking of every lane's OWN trajectory (main.py task_2's result into task_3, per lane): lane b's gains
     come from (x_opt[b], u_opt[b]) and its perturbed starts x0[b] ((B,4), or (B,P,4) for P starts per lane) are
     simulated in closed loop against them.  ``trajectories=False`` returns only the summaries (a Monte-Carlo run has
@@ -244,12 +244,22 @@ def LQR_tracking_lanes(x_opt, u_opt, x0, plant=None, *, trajectories: bool = Tru
     to scalars or arrays broadcastable to (B,P) (names left out: the design model's), or an array (11,), (P,11),
     (B,11), (B,1,11) or (B,P,11) in PARAM_NAMES order, e.g. ``sample_plants(B, P)``; engine.check_plant has the
     rules.  Where plant[b][p] is the design model the results of (b, p) are bit for bit the call's without
-    ``plant``; a plant that drives its loop to inf or NaN shows in that loop's summaries and nowhere else."""
+    ``plant``; a plant that drives its loop to inf or NaN shows in that loop's summaries and nowhere else.
+
+    ``models`` (None: the engine's model on every lane) designs lane b's gains on models[b]: one
+    parameter set per lane in any of engine.check_models' forms, e.g. the ``models`` of the solve that planned the
+    trajectories (SolveResult.models).  Where ``plant`` is not given, closed loop (b, p) is then simulated on
+    models[b] too; an explicit ``plant`` still wins."""
     _check_plant(plant, x_opt, x0)
+    if models is not None and len(np.shape(x_opt)) == 3:
+        models = check_models(models, np.shape(x_opt)[0], PARAM_SETS[_dyn._pset])
+        if plant is None:
+            plant = models[:, None, :]                     # (B,1,11): per lane for every start
     eng = _eng()
     x_opt, u_opt = _lane_trajectories(eng, x_opt, u_opt)
     x0, flat = _lane_starts(eng, x0, x_opt)
-    ws, K = eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=gains)
+    mkw = {} if models is None else {"models": eng.model_table(models, x_opt.shape[0])}
+    ws, K = eng.lqr_lanes_gains(x_opt, u_opt, Q, R, QT, gains=gains, **mkw)
     x, u, s = _lane_rollout(eng, ws, x0, x_opt.shape[1], trajectories, flat, plant)
     return LqrLanesResult(x, u, K, s[0], s[1], s[2])
 

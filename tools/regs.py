@@ -21,7 +21,7 @@ for line in out.splitlines():
     if cur and m:
         rows[cur][m.group(1).strip()] = m.group(2)
 for k, v in rows.items():
-    if "k_nt_" in k or "k_track" in k:
+    if "k_nt_" in k or "k_track" in k or "k_init" in k:
         print(f"{k:42s} VGPR {v.get('VGPRs', '?'):>4}  spillV {v.get('VGPRs Spill', '?'):>3}  "
               f"spillS {v.get('SGPRs Spill', '?'):>3}  scratch {v.get('ScratchSize', '?'):>3}  "
               f"occ {v.get('Occupancy', '?')}")
