@@ -20,11 +20,10 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB_NAME = "libgymnast_acrobot.so"
 LIB_PATH = os.path.join(PKG, LIB_NAME)
 SOURCES = [os.path.join(CSRC, "acrobot_kernels.hip"), os.path.join(CSRC, "tracking_kernels.hip")]
-# everything the library is compiled from: every file of csrc/ (the sources and the headers they include) and the ABI
-# header -- taken from the directory, so that a new header cannot be edited without changing the build id
-DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".h"))) + [
-    os.path.join(INCLUDE, "gymnast_acrobot.h"), os.path.join(INCLUDE, "gymnast_acrobot_box.h"),
-    os.path.join(INCLUDE, "gymnast_acrobot_rk4lin.h"), os.path.join(INCLUDE, "gymnast_acrobot_models.h")]
+# everything the library is compiled from: every file of csrc/ (the sources and the headers they include) and of
+# include/ (the ABI header and its extensions) -- taken from the directories, so that a new header cannot be added or
+# edited without changing the build id
+DEPS = sorted(os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith((".hip", ".hpp", ".h")))
 ARCH = os.environ.get("GYM_OFFLOAD_ARCH", "gfx950")
 BUILD_ID_TAG = b"gym-build-id:"      # marker in front of the id string inside the library's .rodata
 

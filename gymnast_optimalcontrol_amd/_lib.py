@@ -6,13 +6,13 @@ entry point is its prototype in the header and its definition in a .hip file; no
 parser does not understand it refuses with an ImportError (tests/test_abi_binding_host.py checks the result against
 the C compiler's reading of the header).
 
-An extension of the ABI has a header of its own that includes the main one (EXTENSION_HEADERS:
-include/gymnast_acrobot_box.h, the torque-limited Newton solve, include/gymnast_acrobot_rk4lin.h, the RK4-exact
-linearisation; MODELS_HEADER: include/gymnast_acrobot_models.h, per-lane models; ALL_EXTENSION_HEADERS: the three).  It is read by the same parser with the main header's structs and constants known, may declare
-prototypes only, and its entry points are bound beside the others (EXTENSIONS: header -> its entry points, load());
-EXPORTS, the structs and the constants stay the main header's.  EXTENSION_EXPORTS keeps its first meaning, the box
-header's entry points; RK4LIN_EXPORTS are the second header's, MODELS_EXPORTS the third's and ALL_EXPORTS every bound
-entry point.
+An extension of the ABI has a header of its own that includes the main one: every other
+include/gymnast_acrobot_*.h (EXTENSION_HEADERS, from the directory, sorted; today _box.h, the torque-limited Newton
+solve, _models.h, per-lane models, and _rk4lin.h, the RK4-exact linearisation).  It is read by the same parser with
+the main header's structs and constants known, may declare prototypes only, and its entry points are bound beside the
+others (EXTENSIONS: header -> its entry points, load()); EXPORTS, the structs and the constants stay the main
+header's, and ALL_EXPORTS is every bound entry point: EXPORTS, then each extension's in EXTENSION_HEADERS' order.  A
+new extension is its header and its definitions; nothing is added here.
 
 The HIP library is the only compute path of this package.  If it is missing, or no HIP
 device is visible, every compute entry point raises -- there is no CPU fallback.
@@ -123,21 +123,17 @@ with open(os.path.join(_build.INCLUDE, "gymnast_acrobot.h")) as _f:
 EXPORTS = tuple(name for _, name, _ in _ABI.protos)       # every entry point, in the header's order
 _SIGS = {name: [t for t, _ in args] for _, name, args in _ABI.protos if name != "gym_build_id"}
 # the extensions' entry points (prototypes only: no struct, constant or status code of their own)
-EXTENSION_HEADERS = ("gymnast_acrobot_box.h", "gymnast_acrobot_rk4lin.h")   # its first meaning (an existing test's)
-MODELS_HEADER = "gymnast_acrobot_models.h"
-ALL_EXTENSION_HEADERS = EXTENSION_HEADERS + (MODELS_HEADER,)
+EXTENSION_HEADERS = tuple(sorted(f for f in os.listdir(_build.INCLUDE)
+                                 if f.startswith("gymnast_acrobot_") and f.endswith(".h")))
 _EXT_SIGS: dict = {}
 EXTENSIONS: dict = {}
-for _h in ALL_EXTENSION_HEADERS:
+for _h in EXTENSION_HEADERS:
     with open(os.path.join(_build.INCLUDE, _h)) as _f:
         _ext = _parse(_f.read(), base=_ABI)
     if _ext.structs or _ext.status or _ext.consts != _ABI.consts:
         _refuse("an extension header that declares more than prototypes", _h)
     _EXT_SIGS.update({name: [t for t, _ in args] for _, name, args in _ext.protos})
     EXTENSIONS[_h] = tuple(name for _, name, _ in _ext.protos)
-EXTENSION_EXPORTS = EXTENSIONS["gymnast_acrobot_box.h"]
-RK4LIN_EXPORTS = EXTENSIONS["gymnast_acrobot_rk4lin.h"]
-MODELS_EXPORTS = EXTENSIONS[MODELS_HEADER]
 ALL_EXPORTS = EXPORTS + tuple(_EXT_SIGS)
 # every GYM_<NAME> constant and status code under <NAME> (ABI_VERSION, MAX_BP, MPC_MAX_STAGES, FLAG_*, TRACK_SINGLE,
 # CKPT_INTERVAL, TIMING_POOL, ...; ACTIVE ... PAD) and every struct as Gym<Name> (GymModel ... GymBatch)

@@ -25,9 +25,11 @@
 //   newton_stages.hpp    per-lane building blocks: stage cost, rollouts, trial controls, the backward sweeps
 //   newton_lockstep.hpp  serial and pipelined-phase kernels, post-trial Armijo search
 //   newton_run.hpp       the persistent kernels k_nt_run / k_nt_run2
-//   newton_box.hpp       the torque-limited persistent solve k_nt_run_box / k_nt_sigma_box
-//   newton_models.hpp    the persistent solve on per-lane models k_nt_run_models / k_nt_sigma_models
-//   rk4_lin.hpp          the RK4-exact linearisation: k_nt_run_rk4 / k_nt_sigma_rk4, k_linearize_rk4
+//   newton_limited.hpp   the torque-limited persistent solve, once for its variants: k_nt_run_limited and the sigma1
+//                        re-run k_nt_sigma_limited
+//   newton_box.hpp       its plain variant (BoxVariant)
+//   newton_models.hpp    its variant on per-lane models (ModelsVariant)
+//   rk4_lin.hpp          the RK4-exact linearisation: its variant (Rk4Variant), and k_linearize_rk4
 //   newton_tail.hpp      the straggler tail k_nt_tail
 //   newton_util.hpp      API / point kernels, pack / unpack / gather, init, placement probe
 // This file keeps the batch-wide auxiliary kernels (gamma sweeps, statistics, sigma1 re-run, finalize, fill-states),
@@ -52,6 +54,7 @@ namespace {
 #include "newton_stages.hpp"
 #include "newton_lockstep.hpp"
 #include "newton_run.hpp"
+#include "newton_limited.hpp"
 #include "newton_box.hpp"
 #include "newton_models.hpp"
 #include "rk4_lin.hpp"
@@ -849,26 +852,26 @@ int gym_newton_run(const gym_model* m, const gym_weights* w, const gym_armijo* a
     return launch_status();
 }
 
-// gym_newton_run_box / gym_newton_run_rk4: the limited persistent kernel ``kernel_of`` picks (<U0Z, RL>) over the
-// iterations k0 .. k1-1, then the statistics after iteration k1 - 1, as gym_newton_run
-// Args: BoxArgs, or ModelArgs with the per-lane model table of gym_newton_run_models
-extern "C++" template <class Args = BoxArgs, class F>
+// gym_newton_run_box / _rk4 / _models: variant V's persistent kernel over the iterations k0 .. k1-1, then the
+// statistics after iteration k1 - 1, as gym_newton_run
+// (extra: the entry point's arguments that V::extra puts into V::Args, the per-lane model table of ModelsVariant)
+extern "C++" template <class V, class... X>
 static int run_limited(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
-                       const double* tau_max, int32_t k0, int32_t k1, void* s, F&& kernel_of,
-                       const gym_model* models = nullptr) {
+                       const double* tau_max, int32_t k0, int32_t k1, void* s, X... extra) {
     if (!tau_max || bad_iter_args(m, w, a, b) || k0 < 0 || k1 < k0 ||
         (b->flags & (GYM_FLAG_X_CKPT | GYM_FLAG_SIGMA_STREAM)))
         return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     if (k1 > k0) {
         TimedLaunch tl(b->timing, 8, st);
-        Args ra;
+        typename V::Args ra;
         lane_args(ra, m, w, a, b, k0);
         ra.retry_list = b->retry_list; ra.counter = b->counters;
         ra.B = b->B; ra.Bp = b->Bp; ra.N = b->N; ra.k0 = k0; ra.k1 = k1; ra.ext = 0;
         ra.tau = tau_max;
-        if constexpr (std::is_same_v<Args, ModelArgs>) ra.models = models;
-        hipLaunchKernelGGL(with_variant2(b, kernel_of), dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, ra);
+        V::extra(ra, extra...);
+        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_nt_run_limited<V, U0Z(), RL()>; }),
+                           dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, ra);
     }
     launch_stats(b, Range{0, b->B}, (int)k1 - 1, b->counters, b->stats, nullptr, nullptr, st);
     return launch_status();
@@ -876,19 +879,18 @@ static int run_limited(const gym_model* m, const gym_weights* w, const gym_armij
 
 int gym_newton_run_box(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
                        const double* tau_max, int32_t k0, int32_t k1, void* s) {
-    return run_limited(m, w, a, b, tau_max, k0, k1, s, [](auto U0Z, auto RL) { return k_nt_run_box<U0Z(), RL()>; });
+    return run_limited<BoxVariant>(m, w, a, b, tau_max, k0, k1, s);
 }
 
 int gym_newton_run_rk4(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
                        const double* tau_max, int32_t k0, int32_t k1, void* s) {
-    return run_limited(m, w, a, b, tau_max, k0, k1, s, [](auto U0Z, auto RL) { return k_nt_run_rk4<U0Z(), RL()>; });
+    return run_limited<Rk4Variant>(m, w, a, b, tau_max, k0, k1, s);
 }
 
 int gym_newton_run_models(const gym_model* m, const gym_model* models, const gym_weights* w, const gym_armijo* a,
                           const gym_batch* b, const double* tau_max, int32_t k0, int32_t k1, void* s) {
     if (bad_models(models)) return GYM_EINVAL;
-    return run_limited<ModelArgs>(m, w, a, b, tau_max, k0, k1, s,
-                                  [](auto U0Z, auto RL) { return k_nt_run_models<U0Z(), RL()>; }, models);
+    return run_limited<ModelsVariant>(m, w, a, b, tau_max, k0, k1, s, models);
 }
 
 int gym_newton_tail_scratch(int32_t N, int32_t n_lanes, int32_t max_ls, int64_t* doubles_out) {
@@ -1009,16 +1011,17 @@ int gym_newton_sigma(const gym_model* m, const gym_weights* w, const gym_batch* 
                                T, 2, st, b->lane_map);
 }
 
-// gym_newton_sigma_box / gym_newton_sigma_rk4: sigma1 of each lane's last limited sweep by the re-run kernel
-// ``kernel_of`` picks (<U0Z, RL>), one launch per buffer, then sigma unpacked
-// (extra: the kernel's arguments after N, the per-lane model table of gym_newton_sigma_models)
-extern "C++" template <class F, class... X>
+// gym_newton_sigma_box / _rk4 / _models: sigma1 of each lane's last limited sweep by variant V's re-run kernel, one
+// launch per buffer, then sigma unpacked
+// (extra: the kernel's arguments after N, the per-lane model table of ModelsVariant)
+extern "C++" template <class V, class... X>
 static int sigma_limited(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
-                         double* sig_out, void* s, F&& kernel_of, X... extra) {
+                         double* sig_out, void* s, X... extra) {
     if (!m || !w || bad_batch(b) || !tau_max || !sig_out || (b->flags & GYM_FLAG_X_CKPT)) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
+    const auto kern = with_variant2(b, [](auto U0Z, auto RL) { return k_nt_sigma_limited<V, U0Z(), RL(), X...>; });
     for (int parity = 0; parity < 2; ++parity) {
-        hipLaunchKernelGGL(with_variant2(b, kernel_of), dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w),
+        hipLaunchKernelGGL(kern, dim3(grid_for(b->B, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w),
                            (const double2*)b->x[parity], b->u[parity], b->x_ref, b->u_ref, b->cs, tau_max, b->n_iter,
                            parity, b->B, b->Bp, b->N, extra...);
         const int e = launch_status();
@@ -1031,21 +1034,18 @@ static int sigma_limited(const gym_model* m, const gym_weights* w, const gym_bat
 
 int gym_newton_sigma_box(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
                          double* sig_out, void* s) {
-    return sigma_limited(m, w, b, tau_max, sig_out, s,
-                         [](auto U0Z, auto RL) { return k_nt_sigma_box<U0Z(), RL()>; });
+    return sigma_limited<BoxVariant>(m, w, b, tau_max, sig_out, s);
 }
 
 int gym_newton_sigma_rk4(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
                          double* sig_out, void* s) {
-    return sigma_limited(m, w, b, tau_max, sig_out, s,
-                         [](auto U0Z, auto RL) { return k_nt_sigma_rk4<U0Z(), RL()>; });
+    return sigma_limited<Rk4Variant>(m, w, b, tau_max, sig_out, s);
 }
 
 int gym_newton_sigma_models(const gym_model* m, const gym_model* models, const gym_weights* w, const gym_batch* b,
                             const double* tau_max, double* sig_out, void* s) {
     if (bad_models(models) || models_flags(b)) return GYM_EINVAL;
-    return sigma_limited(m, w, b, tau_max, sig_out, s,
-                         [](auto U0Z, auto RL) { return k_nt_sigma_models<U0Z(), RL()>; }, models);
+    return sigma_limited<ModelsVariant>(m, w, b, tau_max, sig_out, s, models);
 }
 
 static int sweep_grid(int64_t Bp, int G) {

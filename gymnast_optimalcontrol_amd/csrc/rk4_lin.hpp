@@ -1,5 +1,5 @@
-// Newton solver kernels: the RK4-exact linearisation and the persistent solve on it, k_nt_run_rk4 / k_nt_sigma_rk4,
-// and the stand-alone primitive k_linearize_rk4.
+// Newton solver kernels: the RK4-exact linearisation, the persistent solve on it (Rk4Variant; gym_newton_run_rk4 /
+// gym_newton_sigma_rk4) and the stand-alone primitive k_linearize_rk4.
 // Part of the acrobot_kernels.hip translation unit (included inside its anonymous namespace, in dependency order).
 #pragma once
 
@@ -134,13 +134,13 @@ __device__ __forceinline__ Rk4Lin rk4_jacobians(const Dyn& m, double x0, double 
 
 // ------------------------------------------------------------------------------------------
 // The sweep on dense stage data: Sweep's P (10 values, symmetric) and p recursion with a full 4x4 A_d and a full
-// b, always in the control-limited form of newton_box.hpp (BoxStage; with tau = +inf no stage is ever clamped).
+// b, always in the control-limited form of newton_limited.hpp (BoxStage; with tau = +inf no stage is ever clamped).
 //   G11 = 2R1 + b^T P b,  F = (P b)^T A_d,  k = -F / G11 (gym::recip),  g1 = r1 + b^T p,  s1u = -g1 / G11
 //   clamped iff s1u < lo or s1u > hi (a NaN is not): k = 0, s1 = the bound, P <- 2Q + A^T P A, p <- q + A^T p + F s1
 //   else: s1 = s1u, P <- 2Q + A^T P A - G11 k k^T, p <- q + A^T p - k G11 s1
 //   dJ += r0 s0 + g1 s1, max|sigma| over s0 and s1.
 // FMA contraction within each expression only, never across statements (as Sweep): the bits do not depend on the
-// kernel the stage is compiled into (k_nt_run_rk4, k_nt_sigma_rk4).
+// kernel the stage is compiled into (the persistent solve, the sigma1 re-run).
 // ------------------------------------------------------------------------------------------
 struct SweepDense {
     double P00, P01, P02, P03, P11, P12, P13, P22, P23, P33, p0, p1, p2, p3;
@@ -303,88 +303,19 @@ __device__ __forceinline__ void backward_solver_lane_rk4(const double2* __restri
     smax_out = S.smax;
 }
 
-// k_nt_run_box on the RK4-exact linearisation: the persistent single-wavefront solve whose sweep is
-// backward_solver_lane_rk4 (always OUT_ALL: sigma1 stored, no re-run for lanes that backtrack).  The trials are the
-// box kernel's (clipped control, the same offset form); the Armijo test, gamma <- beta gamma, the update, the stop
-// test, statuses, counters and histories are k_nt_run's.  tau is always present: an unlimited solve passes +inf.
-// The loop is k_nt_run_box's text again rather than one body both kernels instantiate: through a shared body three of
-// k_nt_run_box's four instantiations compile to other machine code (tools/kernel_isa_diff.py).
-template <bool U0Z, bool RL>
-__global__ __launch_bounds__(BLK, 1) void k_nt_run_rk4(BoxArgs args) {
-    const int64_t l = (int64_t)blockIdx.x * BLK + threadIdx.x;
-    if (l >= args.B) return;
-    int st = kernarg<BoxArgs>()->status[l];
-    for (int k = kernarg<BoxArgs>()->k0; st == GYM_ACTIVE && k < kernarg<BoxArgs>()->k1; ++k) {
-        const int cb = k & 1;
-        {
-            const BoxArgs* R = kernarg<BoxArgs>();
-            double d, s;
-            backward_solver_lane_rk4<U0Z, OUT_ALL>(R->x[cb], R->u[cb], run_xr<RL>(R, l), run_ur<RL>(R, l), R->K1, R->cs,
-                                                   R->a.gamma0, l, R->Bp, R->N, d, s, R->tau[l]);
-            const BoxArgs* Q = kernarg<BoxArgs>();
-            Q->dJ[l] = d;
-            Q->smax[l] = s;
-            if (Q->hist_smax && k < Q->a.hist_len) Q->hist_smax[(int64_t)k * Q->Bp + l] = s;
-        }
-        lane_fence();
-        double Jn;
-        {
-            const BoxArgs* R = kernarg<BoxArgs>();
-            const double2 xa = R->x[cb][wix(0, 0, 2, l, R->Bp)], xb = R->x[cb][wix(0, 1, 2, l, R->Bp)];
-            Jn = rollout_cform<true, U0Z, false, false, kNT, false, 1, true>(
-                R->m, R->w, R->u[cb], R->K1, R->cs, run_xr<RL>(R, l), run_ur<RL>(R, l), R->x[cb ^ 1], R->u[cb ^ 1],
-                R->a.gamma0, R->a.gamma0, l, R->Bp, R->N, xa.x, xa.y, xb.x, xb.y, R->tau[l]);
-        }
-        const BoxArgs* R = kernarg<BoxArgs>();
-        double g = R->a.gamma0;
-        int nr = 1;
-        bool ok = Jn < R->cost[l] + R->a.c * g * R->dJ[l];   // strict Armijo test (:361)
-        for (int j = 1; !ok && j < kernarg<BoxArgs>()->a.max_ls; ++j) {
-            const BoxArgs* P = kernarg<BoxArgs>();
-            g *= P->a.beta;   // gamma_i *= beta, sequentially (:365)
-            const double2 xa = P->x[cb][wix(0, 0, 2, l, P->Bp)], xb = P->x[cb][wix(0, 1, 2, l, P->Bp)];
-            Jn = rollout_cform<true, U0Z, true, false, kNT, false, 1, true>(
-                P->m, P->w, P->u[cb], P->K1, P->cs, run_xr<RL>(P, l), run_ur<RL>(P, l), P->x[cb ^ 1], P->u[cb ^ 1], g,
-                P->a.gamma0, l, P->Bp, P->N, xa.x, xa.y, xb.x, xb.y, P->tau[l]);
-            ++nr;
-            const BoxArgs* Q = kernarg<BoxArgs>();
-            ok = Jn < Q->cost[l] + Q->a.c * g * Q->dJ[l];
-        }
-        const BoxArgs* F = kernarg<BoxArgs>();
-        F->n_roll[l] += nr;
-        F->n_iter[l] += 1;
-        SolverCtl c = F->a;
-        c.k = k;
-        if (ok) {
-            const double s = F->smax[l];
-            accept_lane(c, l, Jn, g, s, F->cost, F->gamma, F->status, F->res_buf, F->hist_cost, F->Bp);
-            if (s < c.tol) st = GYM_CONVERGED;
-        } else {
-            fail_lane(c, l, F->status, F->res_buf);
-            st = GYM_LS_FAILED;
-        }
-        lane_fence();   // the candidate buffer is the next sweep's input
+// The limited solve (newton_limited.hpp) on the RK4-exact linearisation: the sweep is backward_solver_lane_rk4, which
+// reads the model and the weights from the kernel arguments itself; the trials are the box solve's on the batch's model.
+// tau is always present: an unlimited solve passes +inf.
+struct Rk4Variant : BoxVariant {
+    using BoxVariant::BoxVariant;
+    template <bool U0Z, int OUT>
+    static __device__ __forceinline__ void sweep(const Dyn&, const KW&, const double2* x, const double* u,
+                                                 const double* xr, const double* ur, double2* K1, double* cs,
+                                                 double g0, int64_t l, int64_t Bp, int N, double& dJ, double& smax,
+                                                 double tau) {
+        backward_solver_lane_rk4<U0Z, OUT>(x, u, xr, ur, K1, cs, g0, l, Bp, N, dJ, smax, tau);
     }
-}
-
-// sigma1 of each lane's last completed iteration: that iteration's sweep re-run (same inputs, same code: the same
-// bits) into the sigma1 plane.  One launch per buffer parity, as k_nt_sigma_box.
-template <bool U0Z, bool RL>
-__global__ __launch_bounds__(BLK, 1) void k_nt_sigma_rk4(Dyn m, KW w, const double2* __restrict__ x,
-                                                         const double* __restrict__ u, const double* __restrict__ xr,
-                                                         const double* __restrict__ ur, double* __restrict__ cs,
-                                                         const double* __restrict__ tau,
-                                                         const int32_t* __restrict__ n_iter, int parity, int64_t B,
-                                                         int64_t Bp, int N) {
-    const int64_t l = (int64_t)blockIdx.x * BLK + threadIdx.x;
-    if (l >= B) return;
-    const int it = n_iter[l];
-    if (it <= 0 || ((it - 1) & 1) != parity) return;
-    double d, s;
-    backward_solver_lane_rk4<U0Z, OUT_SIGMA>(x, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
-                                             lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), nullptr, cs, 0.0, l, Bp, N, d, s,
-                                             tau[l]);
-}
+};
 
 // build_stage_lists (:166-181) with the RK4-exact A_d, B_d as plain-double SoA for the generic Riccati path:
 // k_linearize's planes and its q, r, q_T expressions.

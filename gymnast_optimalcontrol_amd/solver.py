@@ -32,6 +32,7 @@ from __future__ import annotations
 
 import ctypes as C
 import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -45,6 +46,18 @@ from .results import CHECKPOINT_KEYS, Checkpoint, SolveResult, load_checkpoint  
 
 # _launch arguments of a size query: plain sizes in, a count out; no structure, no stream
 _SIZES = dict(model=False, batch=False, stream=False)
+
+
+class _Kind(NamedTuple):
+    """The kind of solve a solver runs (_set_limited chooses it): ``limited`` names a limited kind in messages (None:
+    the plain solve), then the entry points of its persistent run, sigma re-run, cold and warm start; ``table``:
+    these take the per-lane model table after the model (and one entry point starts cold and warm)."""
+    limited: str | None = None
+    run: str = "gym_newton_run"
+    sigma: str = "gym_newton_sigma"
+    init: str = "gym_newton_init"
+    init_warm: str = "gym_newton_init_warm"
+    table: bool = False
 
 
 class BatchedNewtonSolver:
@@ -168,8 +181,7 @@ class BatchedNewtonSolver:
         if linearization not in ("euler", "rk4"):
             raise ValueError(f'linearization must be "euler" or "rk4", got {linearization!r}')
         self.linearization = linearization
-        self._run_fn, self._sigma_fn = (("gym_newton_run_rk4", "gym_newton_sigma_rk4") if linearization == "rk4" else
-                                        ("gym_newton_run_box", "gym_newton_sigma_box"))
+        self.kind = _Kind()
         self._tau_in = self.tau_buf = None
         self.models = self._models_in = self.models_buf = None
         if models is not None:
@@ -179,13 +191,18 @@ class BatchedNewtonSolver:
             self._models_in = self.eng.model_table(self.models, self.B)          # (B,8) device, the caller's order
             pad = self._models_in[-1:].expand(self.Bp - self.B, -1)              # padding lanes: a valid row
             self.models_buf = torch.cat([self._models_in, pad]).contiguous()    # internal order (init)
-            self._run_fn, self._sigma_fn = "gym_newton_run_models", "gym_newton_sigma_models"
         if tau_max is None and linearization == "euler" and models is None:
             return pipeline, persistent
-        self._limited = ("a torque-limited solve (tau_max)" if tau_max is not None else
-                         'linearization="rk4"' if models is None else "per-lane models (models=)")
+        limit = "a torque-limited solve (tau_max)" if tau_max is not None else None
+        if models is not None:
+            self.kind = _Kind(limit or "per-lane models (models=)", "gym_newton_run_models", "gym_newton_sigma_models",
+                              "gym_newton_init_models", "gym_newton_init_models", table=True)
+        elif linearization == "rk4":
+            self.kind = _Kind(limit or 'linearization="rk4"', "gym_newton_run_rk4", "gym_newton_sigma_rk4")
+        else:
+            self.kind = _Kind(limit, "gym_newton_run_box", "gym_newton_sigma_box")
         if pipeline or checkpoint or persistent is False:
-            raise ValueError(f"{self._limited} runs the persistent schedule only: no pipeline=True, "
+            raise ValueError(f"{self.kind.limited} runs the persistent schedule only: no pipeline=True, "
                              "persistent=False or checkpoint=True")
         if tau_max is None:
             self.tau_buf = torch.full((self.Bp,), float("inf"), dtype=F64, device=self.eng.device)
@@ -372,16 +389,16 @@ class BatchedNewtonSolver:
 
     # --- launches and streams --------------------------------------------------------------
     def _launch(self, name, *args, pre=(), model=True, weights=None, armijo=False, batch=True, stream=True,
-                check=True, table=False):
+                check=True):
         """Call the library's ``name`` as (model[, models], weights[, armijo], *pre, batch, *args, stream) -- the
-        keywords drop or add a part (``weights`` follows ``model`` unless given; ``table``: the per-lane model table
-        of the ..._models entry points) -- and raise on a non-zero return code unless ``check`` is off.  Returns the
-        code."""
+        keywords drop or add a part (``weights`` follows ``model`` unless given); ``models``, the per-lane model
+        table, goes to the entry points of a kind that takes it (_Kind.table) -- and raise on a non-zero return code
+        unless ``check`` is off.  Returns the code."""
         eng = self.eng
         a = []
         if model:
             a.append(C.byref(eng.model))
-        if table:
+        if self.kind.table and name in (self.kind.run, self.kind.sigma, self.kind.init, self.kind.init_warm):
             a.append(self.models_buf.data_ptr())
         if model if weights is None else weights:
             a.append(C.byref(eng._w))
@@ -566,10 +583,8 @@ class BatchedNewtonSolver:
         self._x0 = x0
         if self._pl is not None and self._pl.start(self):
             self._end_placement()
-        if u_init is None and self.models_buf is not None:
-            self._launch("gym_newton_init_models", pre=(x0.data_ptr(), None, None), table=True)
-        elif u_init is None:
-            self._launch("gym_newton_init", pre=(x0.data_ptr(),))
+        if u_init is None:   # (a kind with one entry point for both starts: a warm start without controls)
+            self._launch(self.kind.init, pre=(x0.data_ptr(),) + ((None, None) if self.kind.table else ()))
         else:
             if self.u0_zero and bool((u_init[..., 0] != 0).any().item()):
                 self._set_u0_zero(False)
@@ -578,9 +593,7 @@ class BatchedNewtonSolver:
             # finalize's use of the field)
             self.batch.lane_map = None if _lane_map is None else _lane_map.data_ptr()
             try:
-                self._launch("gym_newton_init_models" if self.models_buf is not None else "gym_newton_init_warm",
-                             pre=(x0.data_ptr(), u_init.data_ptr(), _lib.ptr(status_init)),
-                             table=self.models_buf is not None)
+                self._launch(self.kind.init_warm, pre=(x0.data_ptr(), u_init.data_ptr(), _lib.ptr(status_init)))
             finally:
                 self.batch.lane_map = None
         self.k = 0
@@ -594,11 +607,13 @@ class BatchedNewtonSolver:
 
     def _run(self, k0: int, k1: int):
         self.launches["run"] += 1
-        if self.tau_buf is not None:
-            self._launch(self._run_fn, self.tau_buf.data_ptr(), int(k0), int(k1), armijo=True,
-                         table=self.models_buf is not None)
-        else:
-            self._launch("gym_newton_run", int(k0), int(k1), armijo=True)
+        self._launch(self.kind.run, *self._limits(), int(k0), int(k1), armijo=True)
+
+    _run_fn = property(lambda self: self.kind.run)   # the name a GPU test knows the run entry point by
+
+    def _limits(self) -> tuple:
+        """What a limited kind's run and sigma entry points take first: the per-lane limits."""
+        return () if self.tau_buf is None else (self.tau_buf.data_ptr(),)
 
     def tail_run(self, k0: int, k1: int) -> torch.Tensor:
         """Iterations k0 .. k1-1 of every lane still active, on the straggler-tail kernel (gym_newton_tail: one
@@ -717,7 +732,7 @@ class BatchedNewtonSolver:
         x, u, K, s = (torch.empty((B, *sh), dtype=F64, device=dev) for sh in ((N, 4), (T, 2), (T, 2, 4), (T, 2)))
         if self.tau_buf is not None:   # the limited sigma: the box sweep re-run, never the unlimited one
             self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), None)
-            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr(), table=self.models_buf is not None)
+            self._launch(self.kind.sigma, *self._limits(), s.data_ptr())
         else:
             self._launch("gym_newton_finalize", self.k, x.data_ptr(), u.data_ptr(), K.data_ptr(), s.data_ptr())
         return x, u, K, s
@@ -736,7 +751,7 @@ class BatchedNewtonSolver:
         At the trial step sizes gamma_0 beta^i the values are the Armijo trials' costs bit for bit.  Runs
         iteration k's backward sweep, which that iteration recomputes identically, so the solve is unchanged."""
         if self.tau_buf is not None:
-            raise ValueError(f"gamma_sweep() is not available on a solver with {self._limited}")
+            raise ValueError(f"gamma_sweep() is not available on a solver with {self.kind.limited}")
         g = self.eng.t(gammas).reshape(-1)
         G = int(g.numel())
         if G < 1:
@@ -760,7 +775,7 @@ class BatchedNewtonSolver:
         callers that want every iteration's sigma of a few lanes (the drop-in newton_Algorithm's history).  The same
         bits as any schedule."""
         if self.tau_buf is not None:
-            raise ValueError(f"stream_sigma() is not available on a solver with {self._limited}")
+            raise ValueError(f"stream_sigma() is not available on a solver with {self.kind.limited}")
         if self.k != 0:
             raise RuntimeError("stream_sigma() must follow init() directly")
         self.pipeline = False
@@ -777,10 +792,7 @@ class BatchedNewtonSolver:
             s[..., 0] = -0.0
             return s
         s = torch.empty((self.B, self.T, 2), dtype=F64, device=self.eng.device)
-        if self.tau_buf is not None:
-            self._launch(self._sigma_fn, self.tau_buf.data_ptr(), s.data_ptr(), table=self.models_buf is not None)
-        else:
-            self._launch("gym_newton_sigma", s.data_ptr())
+        self._launch(self.kind.sigma, *self._limits(), s.data_ptr())
         return s
 
     # --- lane compaction ------------------------------------------------------------------

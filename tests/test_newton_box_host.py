@@ -21,8 +21,9 @@ def test_box_entry_points_are_exported_and_check_their_arguments():
     pointers, bad sizes, the flags no box kernel supports) before anything is launched."""
     from gymnast_optimalcontrol_amd import _build, _lib
     lib = _lib.load(_build.build())
-    assert _lib.EXTENSION_EXPORTS == ("gym_newton_run_box", "gym_newton_sigma_box")
-    assert not set(_lib.EXTENSION_EXPORTS) & set(_lib.EXPORTS)      # the main header's ABI is unchanged
+    box = _lib.EXTENSIONS["gymnast_acrobot_box.h"]
+    assert box == ("gym_newton_run_box", "gym_newton_sigma_box")
+    assert not set(box) & set(_lib.EXPORTS)                         # the main header's ABI is unchanged
     P, S = _lib._P, C.POINTER
     assert _lib._EXT_SIGS["gym_newton_run_box"] == [S(_lib.GymModel), S(_lib.GymWeights), S(_lib.GymArmijo),
                                                     S(_lib.GymBatch), P, C.c_int32, C.c_int32, P]

@@ -95,11 +95,14 @@ def test_check_models_forms_and_check_plants_wording():
 
 # ------------------------------------------------------------------------------- the header and its entry points
 def test_models_header_parses_and_its_exports_are_complete():
-    assert _lib.MODELS_EXPORTS == NAMES
-    assert _lib.ALL_EXTENSION_HEADERS == _lib.EXTENSION_HEADERS + ("gymnast_acrobot_models.h",)
-    assert _lib.ALL_EXPORTS == _lib.EXPORTS + _lib.EXTENSION_EXPORTS + _lib.RK4LIN_EXPORTS + _lib.MODELS_EXPORTS
-    assert _lib.EXTENSION_EXPORTS == ("gym_newton_run_box", "gym_newton_sigma_box")
-    assert _lib.RK4LIN_EXPORTS == ("gym_linearize_rk4", "gym_newton_run_rk4", "gym_newton_sigma_rk4")
+    ext = _lib.EXTENSIONS
+    assert ext["gymnast_acrobot_models.h"] == NAMES
+    assert _lib.EXTENSION_HEADERS == ("gymnast_acrobot_box.h", "gymnast_acrobot_models.h", "gymnast_acrobot_rk4lin.h")
+    assert tuple(ext) == _lib.EXTENSION_HEADERS                      # each header's entry points, in the list's order
+    assert _lib.ALL_EXPORTS == (_lib.EXPORTS + ext["gymnast_acrobot_box.h"] + ext["gymnast_acrobot_models.h"] +
+                                ext["gymnast_acrobot_rk4lin.h"])
+    assert ext["gymnast_acrobot_box.h"] == ("gym_newton_run_box", "gym_newton_sigma_box")
+    assert ext["gymnast_acrobot_rk4lin.h"] == ("gym_linearize_rk4", "gym_newton_run_rk4", "gym_newton_sigma_rk4")
     assert not set(NAMES) & set(_lib.EXPORTS)
     assert any(p.endswith("gymnast_acrobot_models.h") for p in _build.DEPS)
     assert any(p.endswith("newton_models.hpp") for p in _build.DEPS)

@@ -82,9 +82,11 @@ def test_rk4lin_entry_points_are_bound_and_check_their_arguments():
     GYM_EINVAL from their host-side checks (the box entry points' conditions) before anything is launched."""
     from gymnast_optimalcontrol_amd import _build, _lib
     lib = _lib.load(_build.build())
-    assert _lib.EXTENSION_HEADERS == ("gymnast_acrobot_box.h", "gymnast_acrobot_rk4lin.h")
-    assert _lib.RK4LIN_EXPORTS == ("gym_linearize_rk4", "gym_newton_run_rk4", "gym_newton_sigma_rk4")
-    assert set(_lib.RK4LIN_EXPORTS) <= set(_lib.ALL_EXPORTS) and not set(_lib.RK4LIN_EXPORTS) & set(_lib.EXPORTS)
+    assert _lib.EXTENSION_HEADERS == ("gymnast_acrobot_box.h", "gymnast_acrobot_models.h", "gymnast_acrobot_rk4lin.h")
+    assert tuple(_lib.EXTENSIONS) == _lib.EXTENSION_HEADERS
+    rk4 = _lib.EXTENSIONS["gymnast_acrobot_rk4lin.h"]
+    assert rk4 == ("gym_linearize_rk4", "gym_newton_run_rk4", "gym_newton_sigma_rk4")
+    assert set(rk4) <= set(_lib.ALL_EXPORTS) and not set(rk4) & set(_lib.EXPORTS)
     assert any(p.endswith("gymnast_acrobot_rk4lin.h") for p in _build.DEPS)
     assert any(p.endswith("rk4_lin.hpp") for p in _build.DEPS)
     P, S = _lib._P, C.POINTER
@@ -92,7 +94,7 @@ def test_rk4lin_entry_points_are_bound_and_check_their_arguments():
     assert _lib._EXT_SIGS["gym_newton_sigma_rk4"] == _lib._EXT_SIGS["gym_newton_sigma_box"]
     assert _lib._EXT_SIGS["gym_linearize_rk4"] == _lib._SIGS["gym_linearize"] == [
         S(_lib.GymModel), S(_lib.GymWeights), P, P, P, P, P, P, P, P, P, C.c_int64, C.c_int64, C.c_int32, P]
-    for name in _lib.RK4LIN_EXPORTS:
+    for name in rk4:
         assert getattr(lib, name).argtypes == _lib._EXT_SIGS[name]
     D = 0x10000
     m, w, a = _lib.GymModel(dt=0.02), _lib.GymWeights(), _lib.GymArmijo(1e-4, 0.7, 0.5, 0.1, 20, 0)

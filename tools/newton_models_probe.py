@@ -2,7 +2,7 @@
 untouched.
 
   a  the cost of per-thread coefficients: kernel time (timing kind 8, HIP events around every launch) of
-     k_nt_run_models on a table of the engine's own rows against k_nt_run_box, both at tau_max = inf: same process,
+     the models kernel on a table of the engine's own rows against the box kernel, both at tau_max = inf: same process,
      4,096 lanes, N = 501, 40 iterations, the two alternated (A B B A A B), three repeats each after one warm-up each
      (the shape and protocol of tools/newton_box_probe.py, arm a), after checking that the two solves' outputs are
      equal bit for bit.  The clocks, power and temperatures of every timed solve are sampled from sysfs

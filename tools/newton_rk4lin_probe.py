@@ -1,7 +1,7 @@
 """Measure the Newton solve on the RK4-exact linearisation (BatchedNewtonSolver(linearization="rk4"),
 gym_newton_run_rk4); bench.py is untouched.
 
-  a  kernel time (timing kind 8, HIP events around every launch) of k_nt_run_rk4 against k_nt_run_box, both at
+  a  kernel time (timing kind 8, HIP events around every launch) of the rk4 kernel against the box kernel, both at
      tau_max = inf: same process, 4,096 lanes, N = 501, 40 iterations, the two alternated (A B B A A B), three
      repeats each after one warm-up each (the shape and protocol of tools/newton_box_probe.py, arm a).
   b  the floor: the 12 starts of tests/golden/lanes.npz at tau_max inf, 18, 16, 14 and tol 1e-4, 1e-5
