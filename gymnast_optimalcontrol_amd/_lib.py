@@ -11,8 +11,15 @@ include/gymnast_acrobot_*.h (EXTENSION_HEADERS, from the directory, sorted; toda
 solve, _models.h, per-lane models, and _rk4lin.h, the RK4-exact linearisation).  It is read by the same parser with
 the main header's structs and constants known, may declare prototypes only, and its entry points are bound beside the
 others (EXTENSIONS: header -> its entry points, load()); EXPORTS, the structs and the constants stay the main
-header's, and ALL_EXPORTS is every bound entry point: EXPORTS, then each extension's in EXTENSION_HEADERS' order.  A
-new extension is its header and its definitions; nothing is added here.
+header's, and ALL_EXPORTS is EXPORTS, then each extension's entry points in EXTENSION_HEADERS' order.
+
+ABI 18's lists are closed: the main header's prototypes, the three extension headers and each one's entry points are
+what its callers and its tests know as ABI 18.  What is added to the library after them is an add-on: any other
+include/*.h (ADDON_HEADERS, from the directory, sorted; today gymnast_newton_weights.h, the Newton solve on per-lane
+cost weights).  An add-on is read by the same parser under the same rule as an extension (_prototypes_only: the main
+header's structs and constants known, prototypes only), and load() binds its entry points beside the others (ADDONS:
+header -> its entry points); EXPORTS, EXTENSION_HEADERS, EXTENSIONS and ALL_EXPORTS do not change with it.  A new
+add-on is its header and its definitions; nothing is added here.
 
 The HIP library is the only compute path of this package.  If it is missing, or no HIP
 device is visible, every compute entry point raises -- there is no CPU fallback.
@@ -117,24 +124,40 @@ def _parse(text: str, base=None):
     return abi
 
 
-with open(os.path.join(_build.INCLUDE, "gymnast_acrobot.h")) as _f:
+_MAIN_HEADER = "gymnast_acrobot.h"
+with open(os.path.join(_build.INCLUDE, _MAIN_HEADER)) as _f:
     _ABI = _parse(_f.read())
 
 EXPORTS = tuple(name for _, name, _ in _ABI.protos)       # every entry point, in the header's order
 _SIGS = {name: [t for t, _ in args] for _, name, args in _ABI.protos if name != "gym_build_id"}
-# the extensions' entry points (prototypes only: no struct, constant or status code of their own)
+
+
+def _prototypes_only(headers, sigs: dict) -> dict:
+    """header -> its entry points for each of ``headers`` (EXTENSION_HEADERS, ADDON_HEADERS), the signatures added to
+    ``sigs``.  The rule for every header beside the main one, stated once: prototypes only -- no struct, constant or
+    status code of its own."""
+    names = {}
+    for h in headers:
+        with open(os.path.join(_build.INCLUDE, h)) as f:
+            ext = _parse(f.read(), base=_ABI)
+        if ext.structs or ext.status or ext.consts != _ABI.consts:
+            _refuse("an extension header that declares more than prototypes", h)
+        sigs.update({name: [t for t, _ in args] for _, name, args in ext.protos})
+        names[h] = tuple(name for _, name, _ in ext.protos)
+    return names
+
+
+# the extensions' entry points
 EXTENSION_HEADERS = tuple(sorted(f for f in os.listdir(_build.INCLUDE)
                                  if f.startswith("gymnast_acrobot_") and f.endswith(".h")))
 _EXT_SIGS: dict = {}
-EXTENSIONS: dict = {}
-for _h in EXTENSION_HEADERS:
-    with open(os.path.join(_build.INCLUDE, _h)) as _f:
-        _ext = _parse(_f.read(), base=_ABI)
-    if _ext.structs or _ext.status or _ext.consts != _ABI.consts:
-        _refuse("an extension header that declares more than prototypes", _h)
-    _EXT_SIGS.update({name: [t for t, _ in args] for _, name, args in _ext.protos})
-    EXTENSIONS[_h] = tuple(name for _, name, _ in _ext.protos)
+EXTENSIONS: dict = _prototypes_only(EXTENSION_HEADERS, _EXT_SIGS)
 ALL_EXPORTS = EXPORTS + tuple(_EXT_SIGS)
+# the add-ons' entry points: every other header of include/ (not part of ALL_EXPORTS, whose list is ABI 18's)
+ADDON_HEADERS = tuple(sorted(f for f in os.listdir(_build.INCLUDE)
+                             if f.endswith(".h") and f != _MAIN_HEADER and f not in EXTENSION_HEADERS))
+_ADDON_SIGS: dict = {}
+ADDONS: dict = _prototypes_only(ADDON_HEADERS, _ADDON_SIGS)
 # every GYM_<NAME> constant and status code under <NAME> (ABI_VERSION, MAX_BP, MPC_MAX_STAGES, FLAG_*, TRACK_SINGLE,
 # CKPT_INTERVAL, TIMING_POOL, ...; ACTIVE ... PAD) and every struct as Gym<Name> (GymModel ... GymBatch)
 globals().update({name[4:]: v for name, v in {**_ABI.consts, **_ABI.status}.items()})
@@ -166,7 +189,7 @@ def load(path: str = LIB_PATH):
         if have != want and not os.environ.get("GYM_ALLOW_FOREIGN_BUILD"):
             raise ImportError(f"{path} was built from other sources (build id {have}, tree {want}): stale binary, "
                               "rebuild it (__graft_entry__.build() or python -m gymnast_optimalcontrol_amd._build)")
-        for name, args in {**_SIGS, **_EXT_SIGS}.items():
+        for name, args in {**_SIGS, **_EXT_SIGS, **_ADDON_SIGS}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = C.c_int

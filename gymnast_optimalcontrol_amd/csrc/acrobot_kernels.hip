@@ -21,7 +21,7 @@
 //
 // One translation unit; the device code lives in headers included below, inside the anonymous namespace and in
 // dependency order:
-//   newton_streams.hpp   kernel-argument constants (Dyn / KW), load / store wrappers, index helpers
+//   newton_streams.hpp   kernel-argument constants (Dyn / KW, kw()), load / store wrappers, index helpers
 //   newton_stages.hpp    per-lane building blocks: stage cost, rollouts, trial controls, the backward sweeps
 //   newton_lockstep.hpp  serial and pipelined-phase kernels, post-trial Armijo search
 //   newton_run.hpp       the persistent kernels k_nt_run / k_nt_run2
@@ -29,6 +29,7 @@
 //                        re-run k_nt_sigma_limited
 //   newton_box.hpp       its plain variant (BoxVariant)
 //   newton_models.hpp    its variant on per-lane models (ModelsVariant)
+//   newton_weights.hpp   its variant on per-lane cost weights (WeightsVariant)
 //   rk4_lin.hpp          the RK4-exact linearisation: its variant (Rk4Variant), and k_linearize_rk4
 //   newton_tail.hpp      the straggler tail k_nt_tail
 //   newton_util.hpp      API / point kernels, pack / unpack / gather, init, placement probe
@@ -45,6 +46,7 @@
 #include "gymnast_acrobot_box.h"
 #include "gymnast_acrobot_rk4lin.h"
 #include "gymnast_acrobot_models.h"
+#include "gymnast_newton_weights.h"
 
 using gym::Dyn;
 
@@ -57,17 +59,10 @@ namespace {
 #include "newton_limited.hpp"
 #include "newton_box.hpp"
 #include "newton_models.hpp"
+#include "newton_weights.hpp"
 #include "rk4_lin.hpp"
 #include "newton_tail.hpp"
 #include "newton_util.hpp"
-
-inline KW kw(const gym_weights& w) {
-    KW k;
-    for (int i = 0; i < 4; ++i) { k.Q[i] = w.Q[i]; k.QT[i] = w.QT[i]; k.twoQ[i] = 2.0 * w.Q[i]; }
-    k.R[0] = w.R[0]; k.R[1] = w.R[1];
-    k.G00 = 2.0 * w.R[0]; k.twoR1 = 2.0 * w.R[1]; k.iG00 = 1.0 / k.G00;
-    return k;
-}
 
 inline int grid_for(int64_t n, int block, int64_t cap = (int64_t)1 << 30) {
     int64_t g = (n + block - 1) / block;
@@ -390,6 +385,18 @@ inline void launch_stats(const gym_batch* b, Range rg, int k, int32_t* counter, 
                        STAT_BLOCKS);
 }
 
+// what a limited solve's sigma is unpacked from: sigma0 recomputed on the batch's weights, or with a per-lane weight
+// table (the entry point's extra argument) on the lane's
+template <class... X>
+SrcSigma sigma_src(const gym_weights* w, const gym_batch* b, X...) {
+    return SrcSigma{kw(*w), b->cs, b->u[0], b->u[1], b->u_ref, b->n_iter,
+                    (b->flags & GYM_FLAG_REF_LANE) ? 2 * (int64_t)(b->N - 1) : 0};
+}
+inline SrcSigmaRows sigma_src(const gym_weights*, const gym_batch* b, const gym_weights* rows) {
+    return SrcSigmaRows{rows, b->cs, b->u[0], b->u[1], b->u_ref, b->n_iter,
+                        (b->flags & GYM_FLAG_REF_LANE) ? 2 * (int64_t)(b->N - 1) : 0};
+}
+
 }  // namespace
 
 // ==========================================================================================
@@ -574,29 +581,25 @@ static hipError_t reset_batch(const gym_batch* b, bool zero_u0, hipStream_t st) 
     return e;
 }
 
-// gym_newton_init / gym_newton_init_warm; models: the (Bp) table of gym_newton_init_models, or null for m on every lane
-static int init_cold(const gym_model* m, const gym_model* models, const gym_weights* w, const double* x0,
-                     const gym_batch* b, void* s) {
+// gym_newton_init / gym_newton_init_warm; table: none, or the (Bp) table of gym_newton_init_models (per-lane models)
+// or gym_newton_init_weights (per-lane weights), which the init kernels take after w
+extern "C++" template <class... Tb>
+static int init_cold(const gym_model* m, const gym_weights* w, const double* x0, const gym_batch* b, void* s,
+                     Tb... table) {
     if (!m || !w || !x0 || bad_batch(b)) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     const hipError_t e = reset_batch(b, true, st);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid(grid_for(b->Bp, BLK));
-    if (models)
-        hipLaunchKernelGGL(with_variant2(b, [](auto, auto RL) { return k_init<RL(), const gym_model*>; }), grid,
-                           dim3(BLK), 0, st, Dyn(*m), kw(*w), models, x0, b->u[0], b->x_ref, b->u_ref,
-                           (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax,
-                           b->dJ, b->B, b->Bp, b->N);
-    else
-        hipLaunchKernelGGL(with_variant2(b, [](auto, auto RL) { return k_init<RL()>; }), grid,
-                           dim3(BLK), 0, st, Dyn(*m), kw(*w), x0, b->u[0], b->x_ref, b->u_ref,
-                           (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax,
-                           b->dJ, b->B, b->Bp, b->N);
+    hipLaunchKernelGGL(with_variant2(b, [](auto, auto RL) { return k_init<RL(), Tb...>; }), dim3(grid_for(b->Bp, BLK)),
+                       dim3(BLK), 0, st, Dyn(*m), kw(*w), table..., x0, b->u[0], b->x_ref, b->u_ref,
+                       (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax,
+                       b->dJ, b->B, b->Bp, b->N);
     return launch_status();
 }
 
-static int init_warm(const gym_model* m, const gym_model* models, const gym_weights* w, const double* x0,
-                     const double* u_init, const int32_t* status_init, const gym_batch* b, void* s) {
+extern "C++" template <class... Tb>
+static int init_warm(const gym_model* m, const gym_weights* w, const double* x0, const double* u_init,
+                     const int32_t* status_init, const gym_batch* b, void* s, Tb... table) {
     if (!m || !w || !x0 || !u_init || bad_batch(b) || ((uintptr_t)u_init & 15)) return GYM_EINVAL;
     hipStream_t st = (hipStream_t)s;
     const int T = b->N - 1;
@@ -608,40 +611,38 @@ static int init_warm(const gym_model* m, const gym_model* models, const gym_weig
                        dim3(TILE_THREADS), 0, st, (const double2*)u_init, b->u[0], b->lane_map, b->B, b->Bp, T);
     int rc = launch_status();
     if (rc) return rc;
-    const dim3 grid(grid_for(b->Bp, BLK));
-    if (models)
-        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) {
-                               return k_init_warm<U0Z(), RL(), const gym_model*>;
-                           }),
-                           grid, dim3(BLK), 0, st, Dyn(*m), kw(*w), models, x0, status_init, b->lane_map, b->u[0],
-                           b->x_ref, b->u_ref, (double2*)b->x[0], b->cost, b->status, b->n_iter, b->res_buf, b->n_roll,
-                           b->gamma, b->smax, b->dJ, b->B, b->Bp, b->N);
-    else
-        hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_init_warm<U0Z(), RL()>; }),
-                           grid, dim3(BLK), 0, st, Dyn(*m), kw(*w), x0,
-                           status_init, b->lane_map, b->u[0], b->x_ref, b->u_ref, (double2*)b->x[0], b->cost, b->status,
-                           b->n_iter, b->res_buf, b->n_roll, b->gamma, b->smax, b->dJ, b->B, b->Bp, b->N);
+    hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_init_warm<U0Z(), RL(), Tb...>; }),
+                       dim3(grid_for(b->Bp, BLK)), dim3(BLK), 0, st, Dyn(*m), kw(*w), table..., x0, status_init,
+                       b->lane_map, b->u[0], b->x_ref, b->u_ref, (double2*)b->x[0], b->cost, b->status, b->n_iter,
+                       b->res_buf, b->n_roll, b->gamma, b->smax, b->dJ, b->B, b->Bp, b->N);
     return launch_status();
 }
 
 int gym_newton_init(const gym_model* m, const gym_weights* w, const double* x0, const gym_batch* b, void* s) {
-    return init_cold(m, nullptr, w, x0, b, s);
+    return init_cold(m, w, x0, b, s);
 }
 
 int gym_newton_init_warm(const gym_model* m, const gym_weights* w, const double* x0, const double* u_init,
                          const int32_t* status_init, const gym_batch* b, void* s) {
-    return init_warm(m, nullptr, w, x0, u_init, status_init, b, s);
+    return init_warm(m, w, x0, u_init, status_init, b, s);
 }
 
-// a per-lane model table (gymnast_acrobot_models.h): present and 16-byte aligned (the rows are read as 16-byte pairs)
-static bool bad_models(const gym_model* models) { return !models || ((uintptr_t)models & 15); }
-// the flags no per-lane-models Newton entry point takes (as the box solve)
-static bool models_flags(const gym_batch* b) { return b && (b->flags & (GYM_FLAG_X_CKPT | GYM_FLAG_SIGMA_STREAM)); }
+// a per-lane table (gymnast_acrobot_models.h, gymnast_newton_weights.h): present and 16-byte aligned (the rows are
+// read as 16-byte pairs)
+static bool bad_table(const void* rows) { return !rows || ((uintptr_t)rows & 15); }
+// the flags no Newton entry point with a per-lane table takes (as the box solve)
+static bool table_flags(const gym_batch* b) { return b && (b->flags & (GYM_FLAG_X_CKPT | GYM_FLAG_SIGMA_STREAM)); }
 
 int gym_newton_init_models(const gym_model* m, const gym_model* models, const gym_weights* w, const double* x0,
                            const double* u_init, const int32_t* status_init, const gym_batch* b, void* s) {
-    if (bad_models(models) || models_flags(b)) return GYM_EINVAL;
-    return u_init ? init_warm(m, models, w, x0, u_init, status_init, b, s) : init_cold(m, models, w, x0, b, s);
+    if (bad_table(models) || table_flags(b)) return GYM_EINVAL;
+    return u_init ? init_warm(m, w, x0, u_init, status_init, b, s, models) : init_cold(m, w, x0, b, s, models);
+}
+
+int gym_newton_init_weights(const gym_model* m, const gym_weights* w, const gym_weights* weights, const double* x0,
+                            const double* u_init, const int32_t* status_init, const gym_batch* b, void* s) {
+    if (bad_table(weights) || table_flags(b)) return GYM_EINVAL;
+    return u_init ? init_warm(m, w, x0, u_init, status_init, b, s, weights) : init_cold(m, w, x0, b, s, weights);
 }
 
 // Grid caps of the post-trial kernels (grid-stride over the retry list; any cap is correct).  They launch every
@@ -852,9 +853,10 @@ int gym_newton_run(const gym_model* m, const gym_weights* w, const gym_armijo* a
     return launch_status();
 }
 
-// gym_newton_run_box / _rk4 / _models: variant V's persistent kernel over the iterations k0 .. k1-1, then the
+// gym_newton_run_box / _rk4 / _models / _weights: variant V's persistent kernel over the iterations k0 .. k1-1, then the
 // statistics after iteration k1 - 1, as gym_newton_run
-// (extra: the entry point's arguments that V::extra puts into V::Args, the per-lane model table of ModelsVariant)
+// (extra: the entry point's arguments that V::extra puts into V::Args, the per-lane table of ModelsVariant or
+// WeightsVariant)
 extern "C++" template <class V, class... X>
 static int run_limited(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
                        const double* tau_max, int32_t k0, int32_t k1, void* s, X... extra) {
@@ -889,8 +891,14 @@ int gym_newton_run_rk4(const gym_model* m, const gym_weights* w, const gym_armij
 
 int gym_newton_run_models(const gym_model* m, const gym_model* models, const gym_weights* w, const gym_armijo* a,
                           const gym_batch* b, const double* tau_max, int32_t k0, int32_t k1, void* s) {
-    if (bad_models(models)) return GYM_EINVAL;
+    if (bad_table(models)) return GYM_EINVAL;
     return run_limited<ModelsVariant>(m, w, a, b, tau_max, k0, k1, s, models);
+}
+
+int gym_newton_run_weights(const gym_model* m, const gym_weights* w, const gym_weights* weights, const gym_armijo* a,
+                           const gym_batch* b, const double* tau_max, int32_t k0, int32_t k1, void* s) {
+    if (bad_table(weights)) return GYM_EINVAL;
+    return run_limited<WeightsVariant>(m, w, a, b, tau_max, k0, k1, s, weights);
 }
 
 int gym_newton_tail_scratch(int32_t N, int32_t n_lanes, int32_t max_ls, int64_t* doubles_out) {
@@ -1011,9 +1019,9 @@ int gym_newton_sigma(const gym_model* m, const gym_weights* w, const gym_batch* 
                                T, 2, st, b->lane_map);
 }
 
-// gym_newton_sigma_box / _rk4 / _models: sigma1 of each lane's last limited sweep by variant V's re-run kernel, one
+// gym_newton_sigma_box / _rk4 / _models / _weights: sigma1 of each lane's last limited sweep by variant V's re-run kernel, one
 // launch per buffer, then sigma unpacked
-// (extra: the kernel's arguments after N, the per-lane model table of ModelsVariant)
+// (extra: the kernel's arguments after N: the per-lane table of ModelsVariant or WeightsVariant)
 extern "C++" template <class V, class... X>
 static int sigma_limited(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
                          double* sig_out, void* s, X... extra) {
@@ -1027,9 +1035,7 @@ static int sigma_limited(const gym_model* m, const gym_weights* w, const gym_bat
         const int e = launch_status();
         if (e) return e;
     }
-    return launch_unpack_tiled(SrcSigma{kw(*w), b->cs, b->u[0], b->u[1], b->u_ref, b->n_iter,
-                                        (b->flags & GYM_FLAG_REF_LANE) ? 2 * (int64_t)(b->N - 1) : 0}, sig_out, b->B, b->Bp,
-                               b->N - 1, 2, st, b->lane_map);
+    return launch_unpack_tiled(sigma_src(w, b, extra...), sig_out, b->B, b->Bp, b->N - 1, 2, st, b->lane_map);
 }
 
 int gym_newton_sigma_box(const gym_model* m, const gym_weights* w, const gym_batch* b, const double* tau_max,
@@ -1044,8 +1050,14 @@ int gym_newton_sigma_rk4(const gym_model* m, const gym_weights* w, const gym_bat
 
 int gym_newton_sigma_models(const gym_model* m, const gym_model* models, const gym_weights* w, const gym_batch* b,
                             const double* tau_max, double* sig_out, void* s) {
-    if (bad_models(models) || models_flags(b)) return GYM_EINVAL;
+    if (bad_table(models) || table_flags(b)) return GYM_EINVAL;
     return sigma_limited<ModelsVariant>(m, w, b, tau_max, sig_out, s, models);
+}
+
+int gym_newton_sigma_weights(const gym_model* m, const gym_weights* w, const gym_weights* weights, const gym_batch* b,
+                             const double* tau_max, double* sig_out, void* s) {
+    if (bad_table(weights) || table_flags(b)) return GYM_EINVAL;
+    return sigma_limited<WeightsVariant>(m, w, b, tau_max, sig_out, s, weights);
 }
 
 static int sweep_grid(int64_t Bp, int G) {

@@ -9,6 +9,8 @@ struct BoxVariant {
     __device__ __forceinline__ BoxVariant(int64_t) {}
     __device__ __forceinline__ BoxVariant(const Dyn&, int64_t) {}
     __device__ __forceinline__ const Dyn& model(const Dyn& m) const { return m; }
+    static constexpr bool LW = false;
+    __device__ __forceinline__ const KW& weights(const KW& w) const { return w; }
     template <bool U0Z, int OUT>
     static constexpr auto sweep = backward_solver_lane_ilp<U0Z, OUT, true>;
 };

@@ -1,6 +1,6 @@
 // Newton solver kernels: the torque-limited (box-constrained) persistent solve k_nt_run_limited and its sigma1 re-run
 // k_nt_sigma_limited, written once for every variant (BoxVariant in newton_box.hpp, Rk4Variant in rk4_lin.hpp,
-// ModelsVariant in newton_models.hpp).
+// ModelsVariant in newton_models.hpp, WeightsVariant in newton_weights.hpp).
 // Part of the acrobot_kernels.hip translation unit (included inside its anonymous namespace, in dependency order).
 #pragma once
 
@@ -25,6 +25,9 @@
 //   V::extra(Args&, table...)    host: fills the fields Args adds to BoxArgs from the entry point's extra arguments
 //   V(l) / V(m, l, table...)     what a thread reads once, before the iteration loop / in the sigma1 re-run
 //   v.model(m)                   the model of one pass, from the batch's (re-read from the kernel arguments per pass)
+//   v.weights(w)                 the cost weights of one pass, from the batch's: w untouched, or this thread's own
+//   V::LW                        whether v.weights(w) is the thread's own, so that the trials take them as handed
+//                                (rollout_cform's LW) instead of re-reading the batch's per stage
 //   V::sweep<U0Z, OUT>(m, ...)   the lane's backward sweep, called with backward_solver_lane_ilp's operands.  Where it
 //                                is that function, V names it (a constexpr alias) rather than wrapping it: through
 //                                one more inlined call the compiler numbers the kernel's registers differently
@@ -34,7 +37,7 @@ struct BoxArgs : RunArgs {
 };
 static_assert(sizeof(BoxArgs) == sizeof(RunArgs) + 8, "kernarg layout: RunArgs, then the limits");
 
-// The persistent kernel of gym_newton_run_box / _rk4 / _models: lane l's outer iterations k0 .. k1-1, as k_nt_run.
+// The persistent kernel of gym_newton_run_box / _rk4 / _models / _weights: lane l's outer iterations k0 .. k1-1, as k_nt_run.
 // The arguments are re-read through kernarg<Args>() at each use (newton_run.hpp: no pointer held across a stage loop).
 template <class V, bool U0Z, bool RL>
 __global__ __launch_bounds__(BLK, 1) void k_nt_run_limited(typename V::Args args) {
@@ -48,7 +51,7 @@ __global__ __launch_bounds__(BLK, 1) void k_nt_run_limited(typename V::Args args
         {
             const Args* R = kernarg<Args>();
             double d, s;
-            V::template sweep<U0Z, OUT_ALL>(v.model(R->m), R->w, R->x[cb], R->u[cb], run_xr<RL>(R, l), run_ur<RL>(R, l),
+            V::template sweep<U0Z, OUT_ALL>(v.model(R->m), v.weights(R->w), R->x[cb], R->u[cb], run_xr<RL>(R, l), run_ur<RL>(R, l),
                                             R->K1, R->cs, R->a.gamma0, l, R->Bp, R->N, d, s, R->tau[l]);
             const Args* Q = kernarg<Args>();
             Q->dJ[l] = d;
@@ -60,8 +63,8 @@ __global__ __launch_bounds__(BLK, 1) void k_nt_run_limited(typename V::Args args
         {
             const Args* R = kernarg<Args>();
             const double2 xa = R->x[cb][wix(0, 0, 2, l, R->Bp)], xb = R->x[cb][wix(0, 1, 2, l, R->Bp)];
-            Jn = rollout_cform<true, U0Z, false, false, kNT, false, 1, true>(
-                v.model(R->m), R->w, R->u[cb], R->K1, R->cs, run_xr<RL>(R, l), run_ur<RL>(R, l), R->x[cb ^ 1],
+            Jn = rollout_cform<true, U0Z, false, false, kNT, false, 1, true, V::LW>(
+                v.model(R->m), v.weights(R->w), R->u[cb], R->K1, R->cs, run_xr<RL>(R, l), run_ur<RL>(R, l), R->x[cb ^ 1],
                 R->u[cb ^ 1], R->a.gamma0, R->a.gamma0, l, R->Bp, R->N, xa.x, xa.y, xb.x, xb.y, R->tau[l]);
         }
         const Args* R = kernarg<Args>();
@@ -72,8 +75,8 @@ __global__ __launch_bounds__(BLK, 1) void k_nt_run_limited(typename V::Args args
             const Args* P = kernarg<Args>();
             g *= P->a.beta;   // gamma_i *= beta, sequentially (:365)
             const double2 xa = P->x[cb][wix(0, 0, 2, l, P->Bp)], xb = P->x[cb][wix(0, 1, 2, l, P->Bp)];
-            Jn = rollout_cform<true, U0Z, true, false, kNT, false, 1, true>(
-                v.model(P->m), P->w, P->u[cb], P->K1, P->cs, run_xr<RL>(P, l), run_ur<RL>(P, l), P->x[cb ^ 1],
+            Jn = rollout_cform<true, U0Z, true, false, kNT, false, 1, true, V::LW>(
+                v.model(P->m), v.weights(P->w), P->u[cb], P->K1, P->cs, run_xr<RL>(P, l), run_ur<RL>(P, l), P->x[cb ^ 1],
                 P->u[cb ^ 1], g, P->a.gamma0, l, P->Bp, P->N, xa.x, xa.y, xb.x, xb.y, P->tau[l]);
             ++nr;
             const Args* Q = kernarg<Args>();
@@ -98,7 +101,8 @@ __global__ __launch_bounds__(BLK, 1) void k_nt_run_limited(typename V::Args args
 
 // sigma1 of each lane's last completed iteration of a limited solve: that iteration's sweep re-run (same inputs, same
 // code: the same bits) into the sigma1 plane.  One launch per buffer parity, as k_nt_sigma's final mode.  table: the
-// entry point's extra arguments (ModelsVariant: the per-lane models), none for the other variants.
+// entry point's extra arguments (ModelsVariant: the per-lane models, WeightsVariant: the per-lane weights), none for
+// the other variants.
 template <class V, bool U0Z, bool RL, class... T>
 __global__ __launch_bounds__(BLK, 1) void k_nt_sigma_limited(Dyn m, KW w, const double2* __restrict__ x,
                                                              const double* __restrict__ u,
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(BLK, 1) void k_nt_sigma_limited(Dyn m, KW w, const 
     if (it <= 0 || ((it - 1) & 1) != parity) return;
     const V v(m, l, table...);
     double d, s;
-    V::template sweep<U0Z, OUT_SIGMA>(v.model(m), w, x, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
+    V::template sweep<U0Z, OUT_SIGMA>(v.model(m), v.weights(w), x, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
                                       lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), nullptr, cs, 0.0, l, Bp, N, d, s,
                                       tau[l]);
 }

@@ -31,6 +31,8 @@ struct ModelsVariant {
         r.h = ka.m.h; r.h2 = ka.m.h2; r.h6 = ka.m.h6;
         return r;
     }
+    static constexpr bool LW = false;
+    __device__ __forceinline__ const KW& weights(const KW& w) const { return w; }
     template <bool U0Z, int OUT>
     static constexpr auto sweep = backward_solver_lane_ilp<U0Z, OUT, true, true>;
 };

@@ -121,8 +121,10 @@ __device__ __forceinline__ double box_clip(double v, double tau) {
 }
 
 // BOX (newton_box.hpp): u1_new clipped to [-tau, tau] before the cost, the store and the RK4 step.
+// LW (newton_weights.hpp): the stage cost on w, this thread's own weights (held in VGPRs); without it the stage cost's
+// Q, R are kernarg_consts()'s, re-read per stage.
 template <bool WRITE, bool U0Z, bool SIG, bool CK = false, int CP = kNT, bool BAND = true, int PD = 1,
-          bool BOX = false>
+          bool BOX = false, bool LW = false>
 __device__ __forceinline__ double rollout_cform(const Dyn& m, const KW& w, const double* __restrict__ u,
                                                 const double2* __restrict__ K1, const double* __restrict__ cs,
                                                 const double* __restrict__ xr, const double* __restrict__ ur,
@@ -166,8 +168,12 @@ __device__ __forceinline__ double rollout_cform(const Dyn& m, const KW& w, const
         double v1 = v1u;
         if constexpr (BOX) v1 = box_clip(v1u, tau);
         const double f0 = U0Z ? 0.0 : v0 - urt[0], f1 = v1 - urt[1];
-        const KArgs ka = kernarg_consts();   // cost weights re-read per stage (no SGPR spills)
-        J = stage_cost<U0Z>(J, ka.w.Q, ka.w.R, n0, n1, n2, n3, xr + 4 * t, f0, f1);
+        if constexpr (LW) {
+            J = stage_cost<U0Z>(J, w.Q, w.R, n0, n1, n2, n3, xr + 4 * t, f0, f1);
+        } else {
+            const KArgs ka = kernarg_consts();   // cost weights re-read per stage (no SGPR spills)
+            J = stage_cost<U0Z>(J, ka.w.Q, ka.w.R, n0, n1, n2, n3, xr + 4 * t, f0, f1);
+        }
         if (WRITE) {
             const auto rO = rsrc(Ob + (int64_t)t * row);
             if (!U0Z) bst1(rO, o1, 0, v0);             // U0Z: the u0 planes stay zero
@@ -575,8 +581,10 @@ __device__ __forceinline__ void backward_solver_lane(const Dyn& m, const KW& w,
 // as backward_solver_lane (step = jacobian + step_j): the same bits.
 // BOX (newton_box.hpp): the sweep of the box solver with the lane's torque limit tau, |u1_t| <= tau on every stage.
 // LM (newton_models.hpp): the stage Jacobians on m, this thread's own model (its nine coefficients in VGPRs); without
-// it m is not read and every constant is kernarg_consts()'s.  dt and the weights are kernarg_consts()'s either way.
-template <bool U0Z, int OUT, bool BOX = false, bool LM = false>
+// it m is not read and every constant is kernarg_consts()'s.  dt is kernarg_consts()'s either way.
+// LW (newton_weights.hpp): the stages' weights are w, this thread's own (held in VGPRs); without it w gives the terminal
+// conditions only and the stages re-read kernarg_consts()'s.
+template <bool U0Z, int OUT, bool BOX = false, bool LM = false, bool LW = false>
 __device__ __forceinline__ void backward_solver_lane_ilp(const Dyn& m, const KW& w,
                                                          const double2* __restrict__ x, const double* __restrict__ u,
                                                          const double* __restrict__ xr, const double* __restrict__ ur,
@@ -615,14 +623,15 @@ __device__ __forceinline__ void backward_solver_lane_ilp(const Dyn& m, const KW&
         if (t >= 1) Jn = jac(n);
         double k0, k1, k2, k3, s0, s1;
         const KArgs ka = kernarg_consts();
+        const KW& sw = LW ? w : ka.w;
         if constexpr (BOX) {
             BoxStage bx;
             bx.lo = -tau - c.u1;
             bx.hi = tau - c.u1;
-            S.step_j<U0Z, true>(ka.m, ka.w, Jc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, k0, k1, k2, k3, s0, s1,
+            S.step_j<U0Z, true>(ka.m, sw, Jc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, k0, k1, k2, k3, s0, s1,
                                 &bx);
         } else {
-            S.step_j<U0Z>(ka.m, ka.w, Jc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, k0, k1, k2, k3, s0, s1);
+            S.step_j<U0Z>(ka.m, sw, Jc, c.xa, c.xb, c.u0, c.u1, xr + 4 * t, ur + 2 * t, k0, k1, k2, k3, s0, s1);
         }
         store_stage<OUT>(Kb, Cb, t, row, plane, o2, o1, c.xa, c.xb, c.u1, g0, k0, k1, k2, k3, s1);
     };

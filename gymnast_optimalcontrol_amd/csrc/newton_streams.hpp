@@ -17,6 +17,16 @@ struct KW {
     double twoQ[4], G00, twoR1, iG00;
 };
 static_assert(sizeof(Dyn) == 12 * sizeof(double) && sizeof(KW) == 17 * sizeof(double), "kernarg layout");
+// KW of one gym_weights, on the host (every entry point's kernel argument) and on the device (a row of a per-lane
+// table, newton_weights.hpp) by these same single-rounded operations: 2x is exact and the reciprocal is the IEEE
+// division on both sides, so a row that equals the batch's weights gives the batch's KW bit for bit.
+__host__ __device__ __forceinline__ KW kw(const gym_weights& w) {
+    KW k;
+    for (int i = 0; i < 4; ++i) { k.Q[i] = w.Q[i]; k.QT[i] = w.QT[i]; k.twoQ[i] = 2.0 * w.Q[i]; }
+    k.R[0] = w.R[0]; k.R[1] = w.R[1];
+    k.G00 = 2.0 * w.R[0]; k.twoR1 = 2.0 * w.R[1]; k.iG00 = 1.0 / k.G00;
+    return k;
+}
 
 // The solver kernels take (Dyn m, KW w, ...) as their FIRST two parameters, i.e. at byte offsets 0 and 96 of
 // the kernel argument segment.  Inside the stage loops the sweep re-reads them from there every stage with

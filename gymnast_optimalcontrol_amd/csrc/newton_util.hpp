@@ -452,10 +452,17 @@ __global__ __launch_bounds__(TILE_THREADS) void k_gather_pack_u(const double2* _
 // and status_init (NULL: l); per-lane references are indexed by the internal lane, as everywhere.
 // Both init kernels: k<...>: every lane rolls out on m; k<..., const gym_model*>: the pack Md is the one parameter
 // after w, the (Bp) table of per-lane models in internal lane order (gym_newton_init_models): lane l rolls out on row
-// l (gym::model_row), dt staying m's.
+// l (gym::model_row), dt staying m's; k<..., const gym_weights*>: the pack is the (Bp) table of per-lane weights
+// (gym_newton_init_weights): lane l's cost is on row l (weights_row, kw()).
 __device__ __forceinline__ const Dyn& init_model(const Dyn& m, int64_t) { return m; }
 __device__ __forceinline__ Dyn init_model(const Dyn& m, int64_t l, const gym_model* rows) {
     return gym::model_row(m, rows, l);
+}
+__device__ __forceinline__ const Dyn& init_model(const Dyn& m, int64_t, const gym_weights*) { return m; }
+__device__ __forceinline__ const KW& init_weights(const KW& w, int64_t) { return w; }
+__device__ __forceinline__ const KW& init_weights(const KW& w, int64_t, const gym_model*) { return w; }
+__device__ __forceinline__ KW init_weights(const KW&, int64_t l, const gym_weights* rows) {
+    return kw(weights_row(rows, l));
 }
 template <bool U0Z, bool RL, class... Md>
 __global__ __launch_bounds__(BLK) void k_init_warm(Dyn m, KW w, Md... models, const double* __restrict__ x0,
@@ -481,7 +488,8 @@ __global__ __launch_bounds__(BLK) void k_init_warm(Dyn m, KW w, Md... models, co
     const int32_t s_in = status_init ? status_init[row] : (int32_t)GYM_ACTIVE;
     status[l] = (s_in == GYM_CONVERGED || s_in == GYM_LS_FAILED) ? s_in : (int32_t)GYM_ACTIVE;
     decltype(auto) lm = init_model(m, l, models...);
-    cost[l] = rollout_warm<U0Z>(lm, w, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
+    decltype(auto) lw = init_weights(w, l, models...);
+    cost[l] = rollout_warm<U0Z>(lm, lw, u, lane_ref<RL>(xr, l, 4 * (int64_t)N),
                                 lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), xn, l, Bp, N, x0[4 * row + 0],
                                 x0[4 * row + 1], x0[4 * row + 2], x0[4 * row + 3]);
 }
@@ -505,7 +513,8 @@ __global__ __launch_bounds__(BLK) void k_init(Dyn m, KW w, Md... models, const d
     }
     status[l] = GYM_ACTIVE;
     decltype(auto) lm = init_model(m, l, models...);
-    cost[l] = rollout_ref<false>(lm, w, nullptr, u, nullptr, nullptr, lane_ref<RL>(xr, l, 4 * (int64_t)N),
+    decltype(auto) lw = init_weights(w, l, models...);
+    cost[l] = rollout_ref<false>(lm, lw, nullptr, u, nullptr, nullptr, lane_ref<RL>(xr, l, 4 * (int64_t)N),
                                  lane_ref<RL>(ur, l, 2 * (int64_t)(N - 1)), xn, nullptr, 0.0, l, Bp, N,
                                  x0[4 * l + 0], x0[4 * l + 1], x0[4 * l + 2], x0[4 * l + 3]);
 }

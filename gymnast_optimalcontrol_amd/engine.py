@@ -100,6 +100,12 @@ class PlantTables:
         return self.plant_table(check_models(models, B, self.params), B, 1).reshape(B, 8)
 
 
+    def weight_table(self, weights, B: int) -> torch.Tensor:
+        """The (B,10) float64 device table of per-lane cost weights (BatchedNewtonSolver's ``weights``), rows in
+        gym_weights' field order (Q[4], R[2], QT[4]): check_weights' forms and refusals, then one upload."""
+        return torch.as_tensor(check_weights(weights, B, self.weights), device=self.device)
+
+
 class AcrobotEngine(PlantTables):
     """Launchers for one acrobot parameter set on one HIP device."""
 
@@ -809,6 +815,48 @@ def check_models(models, B: int, own_params) -> np.ndarray:
         models = {k: (np.asarray(v, dtype=np.float64).reshape(-1, 1) if np.ndim(v) == 1 and k in PARAM_NAMES else v)
                   for k, v in models.items()}
     return check_plant(models, B, 1, own_params).reshape(int(B), 11)
+
+
+def check_weights(weights, B: int, own: Weights) -> np.ndarray:
+    """The cost weights of every lane, (B,10) float64 in gym_weights' field order (Q[4], R[2], QT[4]), from any of
+      * a Weights instance: identical rows;
+      * a dict with the keys "Q", "R", "QT", each (4,) / (2,) for every lane or (B,4) / (B,2) per lane; a key left
+        out takes ``own``'s value (the engine's weights), so {} is the engine's weights on every lane;
+      * an array (10,) or (B,10).
+    Every row must pass Weights.require_gain_solvable (R > 0, Q and Q_T >= 0, all finite).  ValueError, in these words:
+    "unknown weights key" for a key that is none of the three, "weights rows must hold 10 values" for an array's wrong
+    trailing size, "does not broadcast" for a shape that fits none of the forms, and "weights of lane <b>:" followed by
+    require_gain_solvable's own message for the first lane whose row it refuses."""
+    B = int(B)
+    sizes = (("Q", 4), ("R", 2), ("QT", 4))
+    if isinstance(weights, Weights):
+        weights = dict(Q=weights.Q, R=weights.R, QT=weights.QT)
+    if isinstance(weights, dict):
+        unknown = [k for k in weights if k not in ("Q", "R", "QT")]
+        if unknown:
+            raise ValueError(f"unknown weights key {unknown[0]!r}: the keys are Q, R, QT")
+        cols = []
+        for name, n in sizes:
+            v = weights.get(name, getattr(own, name))
+            v = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+            if v.shape not in ((n,), (B, n)):
+                raise ValueError(f"weights[{name!r}] {v.shape} does not broadcast to ({B},{n}): give ({n},) or ({B},{n})")
+            cols.append(np.broadcast_to(v, (B, n)))
+        out = np.concatenate(cols, axis=1)
+    else:
+        a = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64)
+        if a.ndim < 1 or a.shape[-1] != 10:
+            raise ValueError(f"weights rows must hold 10 values (Q[4], R[2], QT[4]), got {a.shape}")
+        if a.shape not in ((10,), (B, 10)):
+            raise ValueError(f"weights {a.shape} does not broadcast to ({B},10): give (10,) or ({B},10)")
+        out = np.broadcast_to(a, (B, 10))
+    out = np.array(out, dtype=np.float64, order="C")      # the caller's array is never aliased
+    for b in range(B):
+        try:
+            Weights(tuple(out[b, :4]), tuple(out[b, 4:6]), tuple(out[b, 6:])).require_gain_solvable()
+        except ValueError as e:
+            raise ValueError(f"weights of lane {b}: {e}") from None
+    return out
 
 
 def check_model_table(table, B: int):

@@ -40,19 +40,22 @@ class SolveResult:
     tau_max: torch.Tensor | None = None     # (B,) per-lane torque limits of a limited solve (None: no limit)
     linearization: str = "euler"            # the sweep's linearisation: "euler" (the reference's) or "rk4"
     models: np.ndarray | None = None        # (B,11) host: the parameter set each lane was planned on (None: the engine's)
+    weights: np.ndarray | None = None       # (B,10) host: Q[4], R[2], QT[4] each lane was planned under (None: the engine's)
 
     def save_npz(self, path, t=None, dt: float = DT):
         """Write the per-lane results as one .npz in the reference's wire format (main.py:74-79, np.savez(x=, u=,
         t=)): x (B,N,4), u (B,T,2), t (N,) = arange(N) * dt unless given, plus cost, status, n_iter, gamma,
         n_rollouts, K and sigma, which load_checkpoint / BatchedNewtonSolver.resume continue from, and
         ``linearization`` where it is not the reference's "euler" (a file without it is an Euler solve's) and
-        ``models`` (B,11) where the lanes were planned on their own (a file without it: on the engine's).  Host I/O
-        only: tensors on any device."""
+        ``models`` (B,11) where the lanes were planned on their own (a file without it: on the engine's) and likewise
+        ``weights`` (B,10) where they were planned under their own.  Host I/O only: tensors on any device."""
         a = {k: getattr(self, k).detach().cpu().numpy() for k in CHECKPOINT_KEYS}
         if self.linearization != "euler":
             a["linearization"] = np.array(self.linearization)
         if self.models is not None:
             a["models"] = np.asarray(self.models, dtype=np.float64)
+        if self.weights is not None:
+            a["weights"] = np.asarray(self.weights, dtype=np.float64)
         N = a["x"].shape[1]
         a["t"] = np.arange(N) * float(dt) if t is None else np.asarray(t, dtype=np.float64)
         if a["t"].shape != (N,):
@@ -131,6 +134,7 @@ class Checkpoint:
     sigma: torch.Tensor      # (B,T,2)
     linearization: str = "euler"   # the sweep the iterates come from; resume() on a solver of the other is refused
     models: np.ndarray | None = None   # (B,11) per-lane parameter sets of the solve; resume() needs the same bits
+    weights: np.ndarray | None = None  # (B,10) per-lane cost weights of the solve; resume() needs the same bits
 
 
 def load_checkpoint(path, device="cpu") -> Checkpoint:
@@ -166,13 +170,14 @@ def load_checkpoint(path, device="cpu") -> Checkpoint:
             full[k] = v
     return Checkpoint(**{k: torch.as_tensor(v).to(device) for k, v in full.items()},
                       linearization=str(a["linearization"]) if "linearization" in a else "euler",
-                      models=_ckpt_models(a, B, path))
+                      models=_ckpt_table(a, "models", (B, 11), path), weights=_ckpt_table(a, "weights", (B, 10), path))
 
 
-def _ckpt_models(a, B, path):
-    if "models" not in a:
+def _ckpt_table(a, key, shape, path):
+    """A per-lane host table of a checkpoint file (models, weights), or None where the file has none."""
+    if key not in a:
         return None
-    m = np.ascontiguousarray(a["models"], dtype=np.float64)
-    if m.shape != (B, 11):
-        raise ValueError(f"{path}: 'models' has shape {m.shape}, expected {(B, 11)}")
+    m = np.ascontiguousarray(a[key], dtype=np.float64)
+    if m.shape != shape:
+        raise ValueError(f"{path}: '{key}' has shape {m.shape}, expected {shape}")
     return m

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib, placement
-from .engine import AcrobotEngine, check_models, padded, F64
+from .engine import AcrobotEngine, check_models, check_weights, padded, F64
 from .host_loop import STAT_FIELDS, morton_order, newton_loop, run_loop, tail_loop  # noqa: F401
 from .params import MAX_LINE_SEARCH_ITERS
 from .placement import PlacementPool
@@ -51,13 +51,14 @@ _SIZES = dict(model=False, batch=False, stream=False)
 class _Kind(NamedTuple):
     """The kind of solve a solver runs (_set_limited chooses it): ``limited`` names a limited kind in messages (None:
     the plain solve), then the entry points of its persistent run, sigma re-run, cold and warm start; ``table``:
-    these take the per-lane model table after the model (and one entry point starts cold and warm)."""
+    these take a per-lane table (and one entry point starts cold and warm): "models", the model table after the model,
+    or "weights", the weight table after the weights."""
     limited: str | None = None
     run: str = "gym_newton_run"
     sigma: str = "gym_newton_sigma"
     init: str = "gym_newton_init"
     init_warm: str = "gym_newton_init_warm"
-    table: bool = False
+    table: str | None = None
 
 
 class BatchedNewtonSolver:
@@ -109,7 +110,7 @@ class BatchedNewtonSolver:
                  capture_sigma=(0, 1, 2), tail_lanes: int | None = None, tail_chunk: int = 128,
                  compact: bool | None = None, world_size: int = 1, cand_slots: int | None = None,
                  arena=False, placement_trials: int | None = None, tau_max=None,
-                 linearization: str = "euler", models=None):
+                 linearization: str = "euler", models=None, weights=None):
         if B <= 0:
             raise ValueError("batch must hold at least one lane")
         engine.weights.require_gain_solvable()
@@ -121,7 +122,8 @@ class BatchedNewtonSolver:
             raise ValueError("max_ls must be >= 1")
         self._set_u0_flag(u0_zero)
         auto_schedule = pipeline is None and persistent is None
-        pipeline, persistent = self._set_limited(tau_max, linearization, models, pipeline, persistent, checkpoint)
+        pipeline, persistent = self._set_limited(tau_max, linearization, models, weights, pipeline, persistent,
+                                                 checkpoint)
         self._choose_schedule(pipeline, persistent, schedule_lanes, checkpoint, chunk, reorder, split_waves)
         self._set_capture(capture_lanes, capture_every, capture_sigma)
         st, placement_trials = self._alloc_streams(arena, placement_trials, auto_schedule)
@@ -170,20 +172,33 @@ class BatchedNewtonSolver:
         self.u0_zero = ref_u0_zero if u0_zero is None else bool(u0_zero)
         self._u0_cleared = False   # the flag is off for one warm-started solve whose u_init has tau1 != 0 (init)
 
-    def _set_limited(self, tau_max, linearization, models, pipeline, persistent, checkpoint):
+    def _set_limited(self, tau_max, linearization, models, weights, pipeline, persistent, checkpoint):
         """The torque limit |tau2| <= tau_max of a limited solve (a number or (B,) per-lane limits, each positive, inf
         allowed), the sweep's linearisation: "euler" (the reference's A_d = I + dt A_c) or "rk4" (the exact
-        Jacobians of the RK4 step), and per-lane models (check_models' forms: lane b is planned on
-        models[b]).  A solver with any of them runs the persistent loop on its own kernel
-        (gym_newton_run_box / gym_newton_run_rk4 / gym_newton_run_models) and nothing else: no pipeline, tail,
-        compaction, low-occupancy switch, checkpointing or candidate scratch.  "rk4" or models without a limit pass
-        +inf limits to that kernel and report none.  Returns (pipeline, persistent) as _choose_schedule takes them."""
+        Jacobians of the RK4 step), per-lane models (check_models' forms: lane b is planned on
+        models[b]) and per-lane cost weights (check_weights' forms: lane b is planned under weights[b],
+        DESIGN 4.12).  A solver with any of them runs the persistent loop on its own kernel (gym_newton_run_box /
+        gym_newton_run_rk4 / gym_newton_run_models / gym_newton_run_weights) and nothing else: no pipeline, tail,
+        compaction, low-occupancy switch, checkpointing or candidate scratch.  "rk4", models or weights without a
+        limit pass +inf limits to that kernel and report none.  Weights combine with neither models nor "rk4" yet.
+        Returns (pipeline, persistent) as _choose_schedule takes them."""
         if linearization not in ("euler", "rk4"):
             raise ValueError(f'linearization must be "euler" or "rk4", got {linearization!r}')
         self.linearization = linearization
         self.kind = _Kind()
         self._tau_in = self.tau_buf = None
         self.models = self._models_in = self.models_buf = None
+        self.lane_weights = self._weights_in = self.weights_buf = None
+        if weights is not None:
+            if models is not None:
+                raise NotImplementedError("per-lane weights (weights=) do not combine with per-lane models (models=) "
+                                          "yet")
+            if linearization == "rk4":
+                raise NotImplementedError('per-lane weights (weights=) do not combine with linearization="rk4" yet')
+            self.lane_weights = check_weights(weights, self.B, self.eng.weights)   # (B,10) host, the caller's order
+            self._weights_in = self.eng.weight_table(self.lane_weights, self.B)    # (B,10) device, the caller's order
+            pad = self.eng.weight_table(self.eng.weights, self.Bp - self.B)        # padding lanes: the engine's
+            self.weights_buf = torch.cat([self._weights_in, pad]).contiguous()     # internal order (init)
         if models is not None:
             if linearization == "rk4":
                 raise ValueError('per-lane models (models=) do not combine with linearization="rk4"')
@@ -191,12 +206,16 @@ class BatchedNewtonSolver:
             self._models_in = self.eng.model_table(self.models, self.B)          # (B,8) device, the caller's order
             pad = self._models_in[-1:].expand(self.Bp - self.B, -1)              # padding lanes: a valid row
             self.models_buf = torch.cat([self._models_in, pad]).contiguous()    # internal order (init)
-        if tau_max is None and linearization == "euler" and models is None:
+        if tau_max is None and linearization == "euler" and models is None and weights is None:
             return pipeline, persistent
         limit = "a torque-limited solve (tau_max)" if tau_max is not None else None
         if models is not None:
             self.kind = _Kind(limit or "per-lane models (models=)", "gym_newton_run_models", "gym_newton_sigma_models",
-                              "gym_newton_init_models", "gym_newton_init_models", table=True)
+                              "gym_newton_init_models", "gym_newton_init_models", table="models")
+        elif weights is not None:
+            self.kind = _Kind(limit or "per-lane weights (weights=)", "gym_newton_run_weights",
+                              "gym_newton_sigma_weights", "gym_newton_init_weights", "gym_newton_init_weights",
+                              table="weights")
         elif linearization == "rk4":
             self.kind = _Kind(limit or 'linearization="rk4"', "gym_newton_run_rk4", "gym_newton_sigma_rk4")
         else:
@@ -390,18 +409,22 @@ class BatchedNewtonSolver:
     # --- launches and streams --------------------------------------------------------------
     def _launch(self, name, *args, pre=(), model=True, weights=None, armijo=False, batch=True, stream=True,
                 check=True):
-        """Call the library's ``name`` as (model[, models], weights[, armijo], *pre, batch, *args, stream) -- the
-        keywords drop or add a part (``weights`` follows ``model`` unless given); ``models``, the per-lane model
-        table, goes to the entry points of a kind that takes it (_Kind.table) -- and raise on a non-zero return code
-        unless ``check`` is off.  Returns the code."""
+        """Call the library's ``name`` as (model[, models], weights[, lane weights][, armijo], *pre, batch, *args,
+        stream) -- the keywords drop or add a part (``weights`` follows ``model`` unless given); ``models`` /
+        ``lane weights``, the per-lane model / weight table, goes to the entry points of a kind that takes it
+        (_Kind.table) -- and raise on a non-zero return code unless ``check`` is off.  Returns the code."""
         eng = self.eng
         a = []
         if model:
             a.append(C.byref(eng.model))
-        if self.kind.table and name in (self.kind.run, self.kind.sigma, self.kind.init, self.kind.init_warm):
+        table = self.kind.table if name in (self.kind.run, self.kind.sigma, self.kind.init,
+                                            self.kind.init_warm) else None
+        if table == "models":
             a.append(self.models_buf.data_ptr())
         if model if weights is None else weights:
             a.append(C.byref(eng._w))
+        if table == "weights":
+            a.append(self.weights_buf.data_ptr())
         if armijo:
             a.append(C.byref(self.armijo))
         a += pre
@@ -580,6 +603,8 @@ class BatchedNewtonSolver:
                 raise ValueError("u_init leaves the torque limit: |u_init[:, :, 1]| <= tau_max must hold per lane")
         if self.models_buf is not None:   # and the per-lane models
             self.models_buf[:self.B] = self._models_in if _ref_perm is None else self._models_in[_ref_perm]
+        if self.weights_buf is not None:  # and the per-lane weights
+            self.weights_buf[:self.B] = self._weights_in if _ref_perm is None else self._weights_in[_ref_perm]
         self._x0 = x0
         if self._pl is not None and self._pl.start(self):
             self._end_placement()
@@ -888,6 +913,8 @@ class BatchedNewtonSolver:
             self.tau_buf[moved] = self.tau_buf[src]
         if self.models_buf is not None:
             self.models_buf[moved] = self.models_buf[src]
+        if self.weights_buf is not None:
+            self.weights_buf[moved] = self.weights_buf[src]
         order = self.lane_order if self.lane_order is not None else torch.arange(B, device=dev)
         self.lane_order = order[perm[:B]]
         self.compactions += 1
@@ -976,7 +1003,8 @@ class BatchedNewtonSolver:
                            compactions=int(self.compactions), lowocc_lane_iterations=int(lowocc),
                            tau_max=None if self._tau_in is None else self._tau_in.clone(),
                            linearization=self.linearization,
-                           models=None if self.models is None else self.models.copy(), **res)
+                           models=None if self.models is None else self.models.copy(),
+                           weights=None if self.lane_weights is None else self.lane_weights.copy(), **res)
 
     def resume(self, ckpt: Checkpoint, max_iters: int, **solve_kw) -> SolveResult:
         """Continue a checkpoint (load_checkpoint) for up to ``max_iters`` further iterations:
@@ -997,6 +1025,10 @@ class BatchedNewtonSolver:
         if (ckpt.models is None) != (self.models is None) or (
                 self.models is not None and ckpt.models.tobytes() != self.models.tobytes()):
             raise ValueError("the checkpoint's per-lane models differ from this solver's (models=): another plant "
+                             "per lane is not the same solve continued")
+        mine, theirs = getattr(self, "lane_weights", None), getattr(ckpt, "weights", None)
+        if (theirs is None) != (mine is None) or (mine is not None and theirs.tobytes() != mine.tobytes()):
+            raise ValueError("the checkpoint's per-lane weights differ from this solver's (weights=): another cost "
                              "per lane is not the same solve continued")
         c = {k: getattr(ckpt, k).to(dev) for k in CHECKPOINT_KEYS}
         if c["x"].ndim != 3 or c["x"].shape[0] != self.B or c["x"].shape[1] != self.N:
@@ -1020,16 +1052,17 @@ def newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, g
                        max_ls=MAX_LINE_SEARCH_ITERS, engine: AcrobotEngine | None = None, hist_len=0,
                        reduce_stats=None, pipeline: bool | None = None,
                        persistent: bool | None = None, capture_lanes=None, u_init=None, tau_max=None,
-                       linearization: str = "euler", models=None) -> SolveResult:
+                       linearization: str = "euler", models=None, weights=None) -> SolveResult:
     """Batched newton_Algorithm: x0 (B,4) -> SolveResult (device tensors).  ``u_init`` (B,T,2): start from these
     controls instead of u = 0 (BatchedNewtonSolver.init).  ``tau_max`` (a number or (B,)): the torque-limited solve
     (BatchedNewtonSolver's tau_max).  ``linearization``: "euler" (the reference's) or "rk4" (the exact Jacobians of
     the RK4 step, BatchedNewtonSolver's linearization).  ``models``: one parameter set per lane, lane b planned on
-    models[b] (BatchedNewtonSolver's models)."""
+    models[b] (BatchedNewtonSolver's models).  ``weights``: one set of cost weights per lane, lane b planned under
+    weights[b] (BatchedNewtonSolver's weights)."""
     eng = engine or AcrobotEngine()
     x0 = eng.t(x0).reshape(-1, 4)
     solver = BatchedNewtonSolver(eng, x_ref, u_ref, x0.shape[0], tol=tol, beta=beta, c=c, gamma_0=gamma_0,
                                  max_ls=max_ls, hist_len=hist_len, pipeline=pipeline, persistent=persistent,
                                  capture_lanes=capture_lanes, tau_max=tau_max, linearization=linearization,
-                                 models=models)
+                                 models=models, weights=weights)
     return solver.solve(x0, max_iters, reduce_stats=reduce_stats, u_init=u_init)

@@ -402,7 +402,7 @@ def newton_Algorithm(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, gam
 def newton_Algorithm_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, gamma_0=1.0,
                            max_ls=MAX_LINE_SEARCH_ITERS, hist_len=0, reduce_stats=None,
                            capture_lanes=None, u_init=None, tau_max=None, linearization: str = "euler",
-                           models=None) -> SolveResult:
+                           models=None, weights=None) -> SolveResult:
     """Batched newton_Algorithm over lanes x0 (B,4) sharing (x_ref, u_ref) -- or each with its own, x_ref (B,N,4) and
     u_ref (B,N-1 or N,2) -- -> SolveResult (device tensors).
     ``hist_len`` keeps every lane's cost / max|sigma| history; ``capture_lanes`` keeps the listed lanes'
@@ -413,11 +413,13 @@ def newton_Algorithm_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.
     README).  ``linearization``: "euler" (the reference's sweep) or "rk4", the exact Jacobians of the RK4 step, with
     which the Armijo search keeps accepting steps down to a small ``tol``.  ``models``: one parameter
     set per lane (engine.check_models' forms, e.g. trajectory_tracking.sample_plants(B, 1)): lane b is planned on
-    models[b] from the first rollout on."""
+    models[b] from the first rollout on.  ``weights``: one set of cost weights Q, R, Q_T per lane
+    (engine.check_weights' forms, e.g. dict(Q=(B,4) array)): lane b is planned under weights[b] from the first cost on
+    (DESIGN 4.12)."""
     return newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=tol, beta=beta, c=c, gamma_0=gamma_0, max_ls=max_ls,
                               engine=_eng(), hist_len=hist_len, reduce_stats=reduce_stats,
                               capture_lanes=capture_lanes, u_init=u_init, tau_max=tau_max,
-                              linearization=linearization, models=models)
+                              linearization=linearization, models=models, weights=weights)
 
 
 def lane_history(res: SolveResult, lane: int) -> dict:
