@@ -21,9 +21,11 @@ LIB_NAME = "libgymnast_acrobot.so"
 LIB_PATH = os.path.join(PKG, LIB_NAME)
 SOURCES = [os.path.join(CSRC, "acrobot_kernels.hip"), os.path.join(CSRC, "tracking_kernels.hip")]
 # everything the library is compiled from: every file of csrc/ (the sources and the headers they include) and of
-# include/ (the ABI header and its extensions) -- taken from the directories, so that a new header cannot be added or
-# edited without changing the build id
-DEPS = sorted(os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith((".hip", ".hpp", ".h")))
+# include/ and include/gymnast/ (the ABI header, its extensions, add-ons and modules) -- taken from the directories, so
+# that a new header cannot be added or edited without changing the build id
+MODULE_DIR = "gymnast"               # include/gymnast/: the headers of the library's modules (_lib.MODULE_HEADERS)
+DEPS = sorted(os.path.join(d, f) for d in (CSRC, INCLUDE, os.path.join(INCLUDE, MODULE_DIR)) if os.path.isdir(d)
+              for f in os.listdir(d) if f.endswith((".hip", ".hpp", ".h")))
 ARCH = os.environ.get("GYM_OFFLOAD_ARCH", "gfx950")
 BUILD_ID_TAG = b"gym-build-id:"      # marker in front of the id string inside the library's .rodata
 

@@ -21,6 +21,12 @@ header's structs and constants known, prototypes only), and load() binds its ent
 header -> its entry points); EXPORTS, EXTENSION_HEADERS, EXTENSIONS and ALL_EXPORTS do not change with it.  A new
 add-on is its header and its definitions; nothing is added here.
 
+A feature added after the add-ons is a module: every .h under include/gymnast/ (MODULE_HEADERS, from the directory,
+sorted, named with the directory as a C file includes them: "gymnast/newton_mpc.h", closed-loop replanning on the Newton
+solver).  A module is read under the same rule (_prototypes_only) and load() binds its entry points beside the others
+(MODULES: header -> its entry points); no other list changes with it, so a new module is its header and its
+definitions, and nothing that pins include/'s own listing moves.
+
 The HIP library is the only compute path of this package.  If it is missing, or no HIP
 device is visible, every compute entry point raises -- there is no CPU fallback.
 """
@@ -133,9 +139,9 @@ _SIGS = {name: [t for t, _ in args] for _, name, args in _ABI.protos if name != 
 
 
 def _prototypes_only(headers, sigs: dict) -> dict:
-    """header -> its entry points for each of ``headers`` (EXTENSION_HEADERS, ADDON_HEADERS), the signatures added to
-    ``sigs``.  The rule for every header beside the main one, stated once: prototypes only -- no struct, constant or
-    status code of its own."""
+    """header -> its entry points for each of ``headers`` (EXTENSION_HEADERS, ADDON_HEADERS, MODULE_HEADERS), the
+    signatures added to ``sigs``.  The rule for every header beside the main one, stated once: prototypes only -- no
+    struct, constant or status code of its own."""
     names = {}
     for h in headers:
         with open(os.path.join(_build.INCLUDE, h)) as f:
@@ -158,6 +164,12 @@ ADDON_HEADERS = tuple(sorted(f for f in os.listdir(_build.INCLUDE)
                              if f.endswith(".h") and f != _MAIN_HEADER and f not in EXTENSION_HEADERS))
 _ADDON_SIGS: dict = {}
 ADDONS: dict = _prototypes_only(ADDON_HEADERS, _ADDON_SIGS)
+# the modules' entry points: every header of include/gymnast/ (part of none of the lists above)
+_MODULE_DIR = os.path.join(_build.INCLUDE, _build.MODULE_DIR)
+MODULE_HEADERS = tuple(sorted(f"{_build.MODULE_DIR}/{f}" for f in (os.listdir(_MODULE_DIR) if os.path.isdir(_MODULE_DIR)
+                                                                    else ()) if f.endswith(".h")))
+_MODULE_SIGS: dict = {}
+MODULES: dict = _prototypes_only(MODULE_HEADERS, _MODULE_SIGS)
 # every GYM_<NAME> constant and status code under <NAME> (ABI_VERSION, MAX_BP, MPC_MAX_STAGES, FLAG_*, TRACK_SINGLE,
 # CKPT_INTERVAL, TIMING_POOL, ...; ACTIVE ... PAD) and every struct as Gym<Name> (GymModel ... GymBatch)
 globals().update({name[4:]: v for name, v in {**_ABI.consts, **_ABI.status}.items()})
@@ -189,7 +201,7 @@ def load(path: str = LIB_PATH):
         if have != want and not os.environ.get("GYM_ALLOW_FOREIGN_BUILD"):
             raise ImportError(f"{path} was built from other sources (build id {have}, tree {want}): stale binary, "
                               "rebuild it (__graft_entry__.build() or python -m gymnast_optimalcontrol_amd._build)")
-        for name, args in {**_SIGS, **_EXT_SIGS, **_ADDON_SIGS}.items():
+        for name, args in {**_SIGS, **_EXT_SIGS, **_ADDON_SIGS, **_MODULE_SIGS}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = C.c_int

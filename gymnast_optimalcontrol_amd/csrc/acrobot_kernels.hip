@@ -28,6 +28,7 @@
 //   newton_limited.hpp   the torque-limited persistent solve, once for its variants: k_nt_run_limited and the sigma1
 //                        re-run k_nt_sigma_limited
 //   newton_box.hpp       its plain variant (BoxVariant)
+//   newton_mpc.hpp       closed-loop replanning on that loop body: k_nt_mpc_run
 //   newton_models.hpp    its variant on per-lane models (ModelsVariant)
 //   newton_weights.hpp   its variant on per-lane cost weights (WeightsVariant)
 //   rk4_lin.hpp          the RK4-exact linearisation: its variant (Rk4Variant), and k_linearize_rk4
@@ -47,6 +48,7 @@
 #include "gymnast_acrobot_rk4lin.h"
 #include "gymnast_acrobot_models.h"
 #include "gymnast_newton_weights.h"
+#include "gymnast/newton_mpc.h"
 
 using gym::Dyn;
 
@@ -58,6 +60,7 @@ namespace {
 #include "newton_run.hpp"
 #include "newton_limited.hpp"
 #include "newton_box.hpp"
+#include "newton_mpc.hpp"
 #include "newton_models.hpp"
 #include "newton_weights.hpp"
 #include "rk4_lin.hpp"
@@ -899,6 +902,31 @@ int gym_newton_run_weights(const gym_model* m, const gym_weights* w, const gym_w
                            const gym_batch* b, const double* tau_max, int32_t k0, int32_t k1, void* s) {
     if (bad_table(weights)) return GYM_EINVAL;
     return run_limited<WeightsVariant>(m, w, a, b, tau_max, k0, k1, s, weights);
+}
+
+// gym_newton_mpc_run: the closed loops' control steps t0 .. t1-1 in one launch of k_nt_mpc_run (newton_mpc.hpp), on the
+// arguments of gym_newton_run_box plus the plant table and the outputs; results go to the caller's rows (lane_map)
+int gym_newton_mpc_run(const gym_model* m, const gym_weights* w, const gym_armijo* a, const gym_batch* b,
+                       const double* tau_max, const gym_model* plant, int32_t t0, int32_t t1, int32_t iters,
+                       double* x_cl, double* u_cl, int32_t* step_iters, int32_t* step_rolls, double* step_cost,
+                       int32_t* step_stop, void* s) {
+    if (!tau_max || bad_table(plant) || bad_iter_args(m, w, a, b) || table_flags(b) || !x_cl || !u_cl ||
+        !step_iters || !step_rolls || !step_cost || !step_stop || t0 < 0 || t1 > b->N - 1 || t0 > t1 || iters < 0)
+        return GYM_EINVAL;
+    if (t1 == t0) return 0;
+    MpcRunArgs ra;
+    lane_args(ra, m, w, a, b, 0);
+    ra.retry_list = b->retry_list; ra.counter = b->counters;
+    ra.B = b->B; ra.Bp = b->Bp; ra.N = b->N; ra.k0 = 0; ra.k1 = 0; ra.ext = 0;
+    ra.tau = tau_max;
+    ra.plant = plant; ra.map = b->lane_map;
+    ra.x_cl = x_cl; ra.u_cl = u_cl; ra.s_iter = step_iters; ra.s_roll = step_rolls; ra.s_cost = step_cost;
+    ra.s_stop = step_stop;
+    ra.t0 = t0; ra.t1 = t1; ra.iters = iters; ra.pad = 0;
+    TimedLaunch tl(b->timing, 8, (hipStream_t)s);
+    hipLaunchKernelGGL(with_variant2(b, [](auto U0Z, auto RL) { return k_nt_mpc_run<BoxVariant, U0Z(), RL()>; }),
+                       dim3(grid_for(b->B, BLK)), dim3(BLK), 0, (hipStream_t)s, ra);
+    return launch_status();
 }
 
 int gym_newton_tail_scratch(int32_t N, int32_t n_lanes, int32_t max_ls, int64_t* doubles_out) {

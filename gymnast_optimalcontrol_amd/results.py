@@ -1,5 +1,6 @@
 """What a batched Newton solve returns and what it continues from: SolveResult (with its .npz writer and the
-tracking front ends on its lanes), Checkpoint and load_checkpoint.  Host I/O and dataclasses only."""
+tracking front ends on its lanes), Checkpoint and load_checkpoint; ClosedLoopResult, what
+BatchedNewtonSolver.closed_loop returns.  Host I/O and dataclasses only."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -114,6 +115,22 @@ class SolveResult:
                 "use track_lqr (which designs each lane on its own model), or pass models=None to track_mpc to say "
                 "that the engine's model is meant")
         return tt.MPC_tracking_lanes(self.x, self.u, self._track_starts(x0, dx0), **kw)
+
+
+@dataclass
+class ClosedLoopResult:
+    """One closed loop per lane under receding-horizon replanning (BatchedNewtonSolver.closed_loop)."""
+    x: torch.Tensor          # (B,N,4)  applied states (n_steps < T: rows 0 .. n_steps, the rest zero)
+    u: torch.Tensor          # (B,T,2)  applied controls
+    iters: torch.Tensor      # (B,T) int32  iterations of each step's replan
+    rollouts: torch.Tensor   # (B,T) int32  rollouts of each step (Armijo trials, and the re-anchor's one)
+    stop: torch.Tensor       # (B,T) int32  _lib.ACTIVE (all iterations ran) / CONVERGED / LS_FAILED per step
+    cost: torch.Tensor       # (B,T)  cost-to-go after each step's replan
+    err_final: torch.Tensor  # (B,)   max |x[:, -1] - x_ref[-1]|, the lane's own reference row
+    u_max: torch.Tensor      # (B,)   largest |torque| applied
+    tau_max: torch.Tensor | None = None     # (B,) per-lane torque limits as given (None: no limit)
+    plant: np.ndarray | None = None         # (B,11) host: the plant each loop ran on (None: the design model)
+    n_steps: int = 0                        # control steps taken
 
 
 CHECKPOINT_KEYS = ("x", "u", "cost", "status", "n_iter", "gamma", "n_rollouts", "K", "sigma")

@@ -42,7 +42,7 @@ from .engine import AcrobotEngine, check_models, check_weights, padded, F64
 from .host_loop import STAT_FIELDS, morton_order, newton_loop, run_loop, tail_loop  # noqa: F401
 from .params import MAX_LINE_SEARCH_ITERS
 from .placement import PlacementPool
-from .results import CHECKPOINT_KEYS, Checkpoint, SolveResult, load_checkpoint  # noqa: F401
+from .results import CHECKPOINT_KEYS, Checkpoint, ClosedLoopResult, SolveResult, load_checkpoint  # noqa: F401
 
 # _launch arguments of a size query: plain sizes in, a count out; no structure, no stream
 _SIZES = dict(model=False, batch=False, stream=False)
@@ -1006,6 +1006,83 @@ class BatchedNewtonSolver:
                            models=None if self.models is None else self.models.copy(),
                            weights=None if self.lane_weights is None else self.lane_weights.copy(), **res)
 
+    # --- closed-loop replanning -------------------------------------------------
+    MPC_RUN = "gym_newton_mpc_run"
+
+    def closed_loop(self, x0, u_init=None, *, iters: int = 1, iters_first: int | None = None, plant=None,
+                    n_steps: int | None = None, steps_per_launch: int | None = None) -> ClosedLoopResult:
+        """One closed loop per lane under receding-horizon replanning (shrinking horizon): init(x0, u_init), then at
+        every control step t up to ``iters`` Newton iterations on the remaining horizon t .. T-1 from the measured
+        state (``iters_first`` at step 0, default ``iters``), warm-started from the previous plan; stage t of the plan
+        is applied to the lane's ``plant``, and where the plant leaves the plan its policy is rolled out again from
+        the measured state (gym_newton_mpc_run, one persistent kernel for the whole loop or per ``steps_per_launch``
+        steps: the same bits).  The stop test comes before the Armijo trials (a converged plan is kept), and either stop
+        ends only its step.  ``plant``: engine.check_models' forms (a set number, a dict, (11,), (B,11), (B,1,11)) and
+        refusals, default the design model on every lane; ``n_steps``: the first steps only (default all T).  A solver
+        without tau_max runs with no limit.  Refused: checkpoint=True; linearization="rk4", models= and weights=
+        (NotImplementedError: the kernel has no instantiation for them yet)."""
+        if self.checkpoint:
+            raise ValueError("closed_loop() needs the full state store: not on a solver with checkpoint=True")
+        for on, what in ((self.linearization == "rk4", 'linearization="rk4"'), (self.models is not None, "models="),
+                         (self.lane_weights is not None, "weights=")):
+            if on:
+                raise NotImplementedError(f"closed_loop() has no kernel for a solver with {what} yet: it replans on "
+                                          "the engine's model, Euler sweep and weights")
+        iters = int(iters)
+        iters_first = iters if iters_first is None else int(iters_first)
+        if iters < 0 or iters_first < 0:
+            raise ValueError(f"iters and iters_first must be >= 0, got {iters} and {iters_first}")
+        n_steps = self.T if n_steps is None else int(n_steps)
+        if not 0 <= n_steps <= self.T:
+            raise ValueError(f"n_steps must lie in 0..{self.T}, got {n_steps}")
+        per = n_steps if steps_per_launch is None else int(steps_per_launch)
+        if steps_per_launch is not None and per < 1:
+            raise ValueError(f"steps_per_launch must be >= 1, got {steps_per_launch}")
+        B, N, T, dev = self.B, self.N, self.T, self.eng.device
+        par = None if plant is None else check_models(plant, B, self.eng.params)      # (B,11) host, the caller's order
+        rows = self.eng.model_table({} if par is None else par, B)                    # (B,8) device, the caller's order
+        x0 = self.eng.t(x0).reshape(-1, 4)
+        perm = morton_order(x0) if self.reorder and B > 1 and x0.shape[0] == B else None
+        # internal lane i is the caller's lane perm[i]: the limits, references and a warm start follow init()'s rules,
+        # the plant rows are permuted here, and the kernel writes internal lane i's results to row perm[i]
+        pad = rows[-1:].expand(self.Bp - B, -1)
+        table = torch.cat([rows if perm is None else rows[perm], pad]).contiguous()
+        if self.tau_buf is None:
+            self._mpc_tau = torch.full((self.Bp,), float("inf"), dtype=F64, device=dev)
+        tau = self.tau_buf if self.tau_buf is not None else self._mpc_tau
+        keep, self.max_iters = self.max_iters, 0          # init() enqueues no solve prologue
+        try:
+            if u_init is None:
+                self.init(x0 if perm is None else x0[perm], _ref_perm=perm)
+            else:
+                self.init(x0, u_init=u_init, _ref_perm=perm, _lane_map=perm)
+        finally:
+            self.max_iters = keep
+        self.lane_order = perm
+        i32 = torch.int32
+        x = torch.zeros((B, N, 4), dtype=F64, device=dev)
+        u = torch.zeros((B, T, 2), dtype=F64, device=dev)
+        it, ro, stop = (torch.zeros((B, T), dtype=i32, device=dev) for _ in range(3))
+        cost = torch.zeros((B, T), dtype=F64, device=dev)
+        outs = tuple(t.data_ptr() for t in (x, u, it, ro, cost, stop))
+        self.batch.lane_map = None if perm is None else perm.data_ptr()
+        try:
+            t = 0
+            while t < n_steps:
+                t1 = 1 if t == 0 else min(t + max(per, 1), n_steps)
+                self._launch(self.MPC_RUN, tau.data_ptr(), table.data_ptr(), t, t1, iters_first if t == 0 else iters,
+                             *outs, armijo=True)
+                t = t1
+        finally:
+            self.batch.lane_map = None
+        xr_last = self._xr_in[:, -1] if self.ref_lane else self.x_ref[-1]
+        return ClosedLoopResult(x=x, u=u, iters=it, rollouts=ro, stop=stop, cost=cost,
+                                err_final=(x[:, n_steps] - xr_last).abs().amax(dim=1) if n_steps == T else
+                                torch.full((B,), float("nan"), dtype=F64, device=dev),
+                                u_max=u.abs().amax(dim=(1, 2)) if T else torch.zeros(B, dtype=F64, device=dev),
+                                tau_max=None if self._tau_in is None else self._tau_in.clone(), plant=par,
+                                n_steps=n_steps)
+
     def resume(self, ckpt: Checkpoint, max_iters: int, **solve_kw) -> SolveResult:
         """Continue a checkpoint (load_checkpoint) for up to ``max_iters`` further iterations:
         solve(ckpt.x[:, 0], max_iters, u_init=ckpt.u, status_init=ckpt.status), merged with the checkpoint.
@@ -1066,3 +1143,19 @@ def newton_solve_batch(x0, x_ref, u_ref, max_iters, tol=1e-6, beta=0.7, c=0.5, g
                                  capture_lanes=capture_lanes, tau_max=tau_max, linearization=linearization,
                                  models=models, weights=weights)
     return solver.solve(x0, max_iters, reduce_stats=reduce_stats, u_init=u_init)
+
+
+def newton_mpc_batch(x0, x_ref, u_ref, tol=1e-6, beta=0.7, c=0.5, gamma_0=1.0, max_ls=MAX_LINE_SEARCH_ITERS,
+                     engine: AcrobotEngine | None = None, u_init=None, tau_max=None, iters: int = 1,
+                     iters_first: int | None = None, plant=None, n_steps: int | None = None,
+                     steps_per_launch: int | None = None) -> ClosedLoopResult:
+    """Batched receding-horizon replanning: x0 (B,4) -> ClosedLoopResult (device tensors), one closed loop per lane
+    (BatchedNewtonSolver.closed_loop).  The settings are newton_solve_batch's; ``iters`` / ``iters_first`` Newton
+    iterations per control step / at step 0, ``plant`` the plant each loop runs on (default: the design model),
+    ``n_steps`` / ``steps_per_launch`` as closed_loop takes them."""
+    eng = engine or AcrobotEngine()
+    x0 = eng.t(x0).reshape(-1, 4)
+    solver = BatchedNewtonSolver(eng, x_ref, u_ref, x0.shape[0], tol=tol, beta=beta, c=c, gamma_0=gamma_0,
+                                 max_ls=max_ls, tau_max=tau_max)
+    return solver.closed_loop(x0, u_init, iters=iters, iters_first=iters_first, plant=plant, n_steps=n_steps,
+                              steps_per_launch=steps_per_launch)

@@ -32,7 +32,7 @@ from .dynamics import (Calculate_A_B_matrixes, continuous_dynamics, dt, dynamics
                        set_params, set_params_numeric, use_params)
 from .engine import Weights
 from .params import MAX_LINE_SEARCH_ITERS
-from .solver import BatchedNewtonSolver, SolveResult, newton_solve_batch  # noqa: F401
+from .solver import BatchedNewtonSolver, SolveResult, newton_mpc_batch, newton_solve_batch  # noqa: F401
 
 T = 10.0
 N = int(T / dt) + 1
